@@ -19,6 +19,33 @@ stream), against the 8.0 TB/s HBM3E peak.  cpu_baseline: the reference codec (co
 workload, on rank 0 after the timed region, with the host cores the job owns (16 per GPU).
 
 usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3|cfg2|cfg1|cfg4]
+                       [--full] [--dump-outputs DIR]
+
+A plain run does what `value` needs and no more: it creates the session, warms up, times the K
+steps (the launches' HIP events give `roofline.frac` in the same pass), finishes the streams for
+`checks.all_recovered`, and prints the line.  --full adds every side measurement and check, each a
+run of its own after the timed region: cpu_baseline, end_to_end, the byte check of the timed
+schedule (checks.digests_match) and the rocprofv3 HBM-traffic passes (roofline.traffic); the
+side workloads' reference legs and per-program breakdown likewise.  The --no-* options take
+single legs out of a --full run.
+
+--steps K times K steps whatever K is.  One session runs at most SESSION_STEPS steps (a stream's
+22-bit packet numbers wrap after 64, where an acknowledged stream's decoder disables itself, in
+the reference codec as here), so a longer run continues in fresh sessions of the same streams,
+each set up and warmed up outside the clock: `value` and `ms_per_step` are over the sessions'
+timed regions together, and `config.sessions` says how many there were.
+
+--dump-outputs DIR writes what a caller of the timed path holds after the last timed step as
+DIR/<name>.npy (float64).  The batched session keeps its packets in HBM and hands its caller the
+summary counters, so those are the arrays (DUMP_FIELDS: the counters that the seeded workload
+fixes; launch and upload counts depend on thread timing and stay out; a long run's sessions are
+summed): `summary_timed` after the
+last timed step, `summary_timed_delta` over the timed steps alone, `summary_finished` after the
+end-of-stream flush.  The packets' bytes are shown by `record_transcript_sha256` (record_digests:
+the first two programs of the same streams once more in record mode after the timed session is
+closed, a fraction of a second; one SHA-256 per stream over the device's digests of every
+recovery packet and recovered original).  Inputs are seeded by stream id: the same arguments give
+the same arrays.  (cfg3 and cfg2 only.)
 
 --gpus N without torch.distributed.run starts N rank processes itself (one per GPU, gloo
 rendezvous on 127.0.0.1); under torch.distributed.run the ranks come from the environment.
@@ -87,10 +114,26 @@ SINGLE_PROGRAM = 4096  # cfg1 / cfg4 (profiles/r06_single_step_sweep.txt)
 # `--steps 20` then times ~110 ms instead of ~28 ms.  The inputs are a pool of INPUT_POOL rows per
 # side per stream that original i reads as row i mod INPUT_POOL (tonk_amd.h input_pool).
 PROGRAMS_PER_STEP = 65536 // ORIGINALS_PER_STEP
+SESSION_STEPS = 60  # bench steps one session runs, below the 64 at which packet numbers wrap (main)
 INPUT_POOL = 65536
 LOSS = 0.01
 ACK = 64
 PAYLOAD = 1300
+# --dump-outputs: the summary counters that the seeded workload determines (tonk_amd.SUMMARY_FIELDS
+# without the launch / merge / upload / staging counts, which follow thread and device timing)
+DUMP_FIELDS = ("originals", "lost_originals", "recoveries", "lost_recoveries", "recovered", "arq",
+               "missing_at_end", "payload_bytes", "alg_bytes", "acc_bytes", "store_bytes", "disabled_codecs")
+
+
+def dump_outputs(out_dir: str, arrays: dict, rank: int = 0) -> None:
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64 (rank r > 0 of a multi-GPU
+    job: <name>.rank<r>.npy).  The counters stay below 2^53, so float64 holds them exactly."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, values in arrays.items():
+        arr = np.asarray(values, dtype=np.float64)
+        assert arr.nbytes <= 64 << 20, name
+        np.save(os.path.join(out_dir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"), arr)
 
 
 def host_threads(local_world: int) -> int:
@@ -260,6 +303,29 @@ def verify_schedule(threads: int, device: int) -> dict:
                          f"{threads} host threads, one pass per step")}
 
 
+def record_digests(threads: int, device: int, loss: float, base: int, programs: int = 2) -> list[list[int]]:
+    """--dump-outputs: the bytes behind the counters.  The timed session leaves its packets in HBM
+    at addresses that follow thread and device timing, so they are shown another way: the first
+    `programs` programs of the same streams (same seeds, loss, acks, program size, threads and
+    schedule) run once more in record mode, where every recovery packet and every recovered
+    original is digested on the launch stream, and each stream's transcript (those digests, the
+    acknowledgements and the decode results, in order) is reduced to its SHA-256: one row of 32
+    byte values per stream."""
+    import hashlib
+    n = programs * ORIGINALS_PER_STEP
+    wp = tonk_amd.WorkloadParams(n=n, payload=PAYLOAD, loss=loss, ack=ACK)
+    sess = tonk_amd.Session(wp, n_streams=STREAMS_PER_GPU, device=device, stream_base=base, threads=threads,
+                            arena_bytes=2 * n * STREAMS_PER_GPU * 1344 + (4 << 30), record=True)
+    try:
+        sess.generate()
+        for _ in range(programs):
+            sess.step(ORIGINALS_PER_STEP)
+        sess.finish()
+        return [list(hashlib.sha256(sess.transcript(i).encode()).digest()) for i in range(STREAMS_PER_GPU)]
+    finally:
+        sess.close()
+
+
 def end_to_end(threads: int, device: int, loss: float, steps: int = 3, warmup: int = 1) -> dict | None:
     """The PCIe-inclusive rate (north_star): the same workload with packets starting
     and ending in pinned host memory -- copies on their own streams, overlapped with the codec
@@ -331,15 +397,16 @@ BATCHED = {
 }
 
 
-def single_stream(name: str, device: int, step: int, reps: int = 3) -> dict:
+def single_stream(name: str, device: int, step: int, reps: int = 3, full: bool = False) -> dict:
     """One connection stream run start to finish (generate untimed; steps of 4096 originals,
-    end-of-stream flush and device sync timed), the median of `reps` fresh sessions, next to the
-    reference codec on one host thread over the same stream."""
+    end-of-stream flush and device sync timed), the median of `reps` fresh sessions; with `full`,
+    next to the reference codec on one host thread over the same stream, and with the
+    per-program breakdown of one more run."""
     wp = tonk_amd.WorkloadParams(payload=PAYLOAD, **SINGLE_STREAM[name])
-    times, payload, ok, runs = [], 0, True, []
+    times, payload, ok, breakdown = [], 0, True, None
     # The timed reps run without per-launch timing events (they add ~20 us of event work to a
     # single stream's few launches); one more rep with them gives the per-program breakdown.
-    for rep in range(reps + 1):
+    for rep in range(reps + (1 if full else 0)):
         timed = rep < reps
         sess = tonk_amd.Session(wp, n_streams=1, device=device, threads=1, arena_bytes=(3 * wp.n * 1344) + (1 << 30))
         try:
@@ -385,7 +452,7 @@ def single_stream(name: str, device: int, step: int, reps: int = 3) -> dict:
                       "originals_per_step": step},
            "checks": {"all_recovered": ok}, "per_program": breakdown, "cpu_baseline": None}
     exe = os.path.join(ROOT, "oracle", "_ref", "golden_gen")
-    if os.path.exists(exe):
+    if full and os.path.exists(exe):
         def run(r: int) -> dict | None:
             res = subprocess.run([exe, "time", "threads=1", "streams=1", f"reps={r}"] + wp.args(),
                                  capture_output=True, text=True, timeout=600)
@@ -400,15 +467,15 @@ def single_stream(name: str, device: int, step: int, reps: int = 3) -> dict:
     return out
 
 
-def capi_bench(threads: int, runs: int = 3) -> dict:
+def capi_bench(threads: int, runs: int = 3, full: bool = False) -> dict:
     """`--workload capi`: the drop-in path Tonk actually links -- libtonk_amd.so through the
     siamese.h C ABI (every siamese_encode / siamese_decode is one synchronous program on the GPU
     and a readback; siamese.cpp:158-167 / TonkineseOutgoing.cpp:1284-1328 call it inline) -- on
     BASELINE.json configs[2] (64 streams x 4096 originals, 2% loss, f = 4%, ack every 64), each
     stream's codec pair driven by the same workload loop on `threads` host threads
     (tests/native/_build/capi_gen: oracle/golden_gen.cpp linked against our library), beside the
-    reference codec with the same arguments (oracle/_ref/golden_gen).  Reports GiB/s and the per-call
-    latency percentiles of siamese_encode and siamese_decode for both."""
+    reference codec with the same arguments (oracle/_ref/golden_gen; with `full` only).  Reports
+    GiB/s and the per-call latency percentiles of siamese_encode and siamese_decode for both."""
     n, loss = 4096, 0.02
     wp = tonk_amd.WorkloadParams(n=n, payload=PAYLOAD, loss=loss, ack=ACK)
     common = ["time", f"threads={threads}", f"streams={STREAMS_PER_GPU}", "reps=1", f"runs={runs}", "lat=1"] + wp.args()
@@ -427,7 +494,7 @@ def capi_bench(threads: int, runs: int = 3) -> dict:
                 "encode_us": med.get("encode_us"), "decode_us": med.get("decode_us"), "bad": med["bad"]}
 
     ours = leg(os.path.join(ROOT, "tests", "native", "_build", "capi_gen"))
-    ref = leg(os.path.join(ROOT, "oracle", "_ref", "golden_gen"))
+    ref = leg(os.path.join(ROOT, "oracle", "_ref", "golden_gen")) if full else None
     line = {"metric": "Siamese FEC encode+decode GiB/s through the siamese.h C ABI (host buffers, per-call programs)",
             "value": ours.get("value") if ours else None, "unit": "GiB/s", "n_gpus": 1, "higher_is_better": True,
             "dtype": "u8", "data": "synthetic",
@@ -476,8 +543,8 @@ def compress_messages(n_streams: int, n_msgs: int, seed: int = 7):
 
 def compress_bench(device: int, steps: int, warmup: int, cpu: bool) -> dict:
     """`--workload compress`: SURVEY s8(f)4, Tonk's MessageCompressor (PacketCompression.h:92)
-    on 64 streams x 1024 messages per step, device resident; the reference compressor (zstd level
-    1 over the same ring, oracle/_ref/libmsgcodec_ref.so) on 16 host threads beside it."""
+    on 64 streams x 1024 messages per step, device resident; with `cpu`, the reference compressor
+    (zstd level 1 over the same ring, oracle/_ref/libmsgcodec_ref.so) on 16 host threads beside it."""
     import ctypes
     import torch
     from tonk_amd.compress import compress_batch
@@ -697,10 +764,15 @@ def main() -> int:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-end-to-end", action="store_true", help="skip the PCIe-inclusive side measurement")
-    ap.add_argument("--no-verify", action="store_true", help="skip the untimed byte check of the timed schedule")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 HBM-traffic passes (roofline.traffic)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements and checks: cpu_baseline, end_to_end, the byte check "
+                         "of the timed schedule and the rocprofv3 HBM-traffic passes (each a run of its own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned after its last timed step as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the reference codec's CPU leg")
+    ap.add_argument("--no-end-to-end", action="store_true", help="--full without the PCIe-inclusive side measurement")
+    ap.add_argument("--no-verify", action="store_true", help="--full without the untimed byte check of the timed schedule")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 HBM-traffic passes (roofline.traffic)")
     ap.add_argument("--workload", choices=sorted(BATCHED) + sorted(SINGLE_STREAM) + ["compress", "capi"], default="cfg3",
                     help="BASELINE.json configs[] index: cfg3 (the headline, 64 streams per GPU), cfg2 (64 "
                          "streams, 2%% loss), cfg1 / cfg4 (one stream, start to finish)")
@@ -709,6 +781,8 @@ def main() -> int:
     ap.add_argument("--dry-run", action="store_true",
                     help="form the ranks and print the shard plan without touching a GPU (tests)")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     world = int(os.environ.get("WORLD_SIZE", "0") or 0)
     if world == 0:
@@ -729,19 +803,23 @@ def main() -> int:
         line_out = os.fdopen(os.dup(1), "w")
         os.dup2(2, 1)
 
+    if a.dump_outputs and a.workload not in BATCHED:
+        print(f"bench.py: --dump-outputs is for the batched workloads, not --workload {a.workload}", file=sys.stderr)
+        return 2
+
     if a.workload == "compress":  # SURVEY s8(f)4 side line (not the headline)
         if world > 1:
             print("bench.py: the compress workload runs on one GPU", file=sys.stderr)
             return 2
-        print(json.dumps(compress_bench(local_rank, min(a.steps, 10), min(a.warmup, 2), not a.no_cpu_baseline)),
-              flush=True)
+        print(json.dumps(compress_bench(local_rank, min(a.steps, 10), min(a.warmup, 2),
+                                        a.full and not a.no_cpu_baseline)), flush=True)
         return 0
 
     if a.workload == "capi":  # the siamese.h drop-in path (side line, not the headline)
         if world > 1:
             print("bench.py: the capi workload runs on one GPU", file=sys.stderr)
             return 2
-        print(json.dumps(capi_bench(host_threads(1))), flush=True)
+        print(json.dumps(capi_bench(host_threads(1), full=a.full and not a.no_cpu_baseline)), flush=True)
         return 0
 
     if a.workload in SINGLE_STREAM:
@@ -749,7 +827,7 @@ def main() -> int:
             print("bench.py: single-stream workloads run on one GPU (replicas only)", file=sys.stderr)
             return 2
         step = a.step or SINGLE_PROGRAM
-        print(json.dumps(single_stream(a.workload, local_rank, step)), flush=True)
+        print(json.dumps(single_stream(a.workload, local_rank, step, full=a.full)), flush=True)
         return 0
 
     loss = BATCHED[a.workload]["loss"]
@@ -780,68 +858,98 @@ def main() -> int:
     threads = host_threads(local_world)
     total_steps = a.warmup + a.steps
     n_orig = total_steps * ORIGINALS_PER_STEP * PROGRAMS_PER_STEP
-    wp = tonk_amd.WorkloadParams(n=n_orig, payload=PAYLOAD, loss=loss, ack=ACK)
+    # One session times at most SESSION_STEPS steps, warm-up included: a stream's packet numbers
+    # wrap after 2^22 originals (64 steps), where the reference decoder of an acknowledged stream
+    # disables itself and ours does the same.  A longer run goes on in fresh sessions of the same
+    # streams, each created, filled and warmed up outside the clock; the timed region is the sum
+    # of the sessions' timed regions.  (Up to SESSION_STEPS steps in all: one session, as before.)
+    warm = a.warmup if total_steps <= SESSION_STEPS else min(a.warmup, SESSION_STEPS // 2)
+    plan, left = [], a.steps
+    while left > 0:
+        plan.append(min(left, SESSION_STEPS - warm))
+        left -= plan[-1]
     # TONK_AMD_BENCH_DEVICE: every rank on this device -- a rehearsal of the N-rank path on a
     # one-GPU box (the ranks then share one GPU and its host cores: not a scaling measurement)
     device = int(os.environ.get("TONK_AMD_BENCH_DEVICE", local_rank))
     if "TONK_AMD_BENCH_DEVICE" in os.environ and local_world > 1 and "TONK_AMD_CPU_SLOT" not in os.environ:
         os.environ["TONK_AMD_CPU_SLOT"] = f"{local_rank}/{local_world}"  # (disjoint cores all the same)
     pool = min(INPUT_POOL, n_orig)
-    sess = tonk_amd.Session(wp, n_streams=STREAMS_PER_GPU, device=device,
-                            stream_base=stream_base(rank), threads=threads,
-                            arena_bytes=(2 * pool * STREAMS_PER_GPU * 1344) + (4 << 30), input_pool=pool)
-    sess.generate()
-    sess_cpus = sess.cpus()
-    rank_cores = d.gather(pad_cores(sess_cpus))
+    # sums over the sessions (one session: that session's own figures)
+    own_s = elapsed = kernel_ms = 0.0
+    launches, ok, rank_cores = 0, True, None
+    s0, s1, fin = ({k: 0 for k in tonk_amd.SUMMARY_FIELDS} for _ in range(3))
+    host_sum = {}
+    for timed_steps in plan:
+        wp = tonk_amd.WorkloadParams(n=(warm + timed_steps) * ORIGINALS_PER_STEP * PROGRAMS_PER_STEP,
+                                     payload=PAYLOAD, loss=loss, ack=ACK)
+        sess = tonk_amd.Session(wp, n_streams=STREAMS_PER_GPU, device=device,
+                                stream_base=stream_base(rank), threads=threads,
+                                arena_bytes=(2 * pool * STREAMS_PER_GPU * 1344) + (4 << 30), input_pool=pool)
+        sess.generate()
+        if rank_cores is None:
+            sess_cpus = sess.cpus()
+            rank_cores = d.gather(pad_cores(sess_cpus))
 
-    for _ in range(a.warmup * PROGRAMS_PER_STEP):
-        sess.step(ORIGINALS_PER_STEP)
-    sess.wait()
-    s0 = sess.summary()
-    h0 = sess.host_ms()
-    sess.set_timing(True)
-    d.barrier()
-    env = HostEnv(sess.cpus())
-    t0 = time.perf_counter()
-    for _ in range(a.steps * PROGRAMS_PER_STEP):
-        sess.step(ORIGINALS_PER_STEP)
-    sess.wait()
-    t1 = time.perf_counter()
-    host_env = env.report()
-    host_env["heap"] = "glibc hugetlb (THP)" if "glibc.malloc.hugetlb=1" in os.environ.get("GLIBC_TUNABLES", "") \
-        else "glibc default"
-    d.barrier()
-    sess.set_timing(False)
-    kernel_ms, launches = sess.kernel_ms()
-    arena_base, arena_bytes = sess.arena()
-    s1 = sess.summary()
-    h1 = sess.host_ms()
+        for _ in range(warm * PROGRAMS_PER_STEP):
+            sess.step(ORIGINALS_PER_STEP)
+        sess.wait()
+        a0 = sess.summary()
+        h0 = sess.host_ms()
+        sess.set_timing(True)
+        d.barrier()
+        env = HostEnv(sess.cpus())
+        t0 = time.perf_counter()
+        for _ in range(timed_steps * PROGRAMS_PER_STEP):
+            sess.step(ORIGINALS_PER_STEP)
+        sess.wait()
+        t1 = time.perf_counter()
+        host_env = env.report()  # (of the last session)
+        host_env["heap"] = "glibc hugetlb (THP)" if "glibc.malloc.hugetlb=1" in os.environ.get("GLIBC_TUNABLES", "") \
+            else "glibc default"
+        d.barrier()
+        sess.set_timing(False)
+        k_ms, k_n = sess.kernel_ms()
+        kernel_ms, launches = kernel_ms + k_ms, launches + k_n
+        arena_base, arena_bytes = sess.arena()
+        a1 = sess.summary()
+        h1 = sess.host_ms()
+        host_sum = {k: host_sum.get(k, 0.0) + h1[k] - h0[k] for k in h1}
+        own_s += t1 - t0
+        elapsed += d.allmax(t1 - t0)
+
+        # Correctness of the run itself: finish the streams (lossless flush) and require that every
+        # original was received or recovered and no codec was disabled.
+        sess.finish()
+        af = sess.summary()
+        ok = ok and af["missing_at_end"] == 0 and af["disabled_codecs"] == 0
+        sess.close()
+        for tot, part in ((s0, a0), (s1, a1), (fin, af)):
+            for k in tot:
+                tot[k] += part[k]
     # per device program (a quarter of a bench step)
-    host = {k: round((h1[k] - h0[k]) / (a.steps * PROGRAMS_PER_STEP), 4) for k in h1}
-    elapsed = d.allmax(t1 - t0)
+    host = {k: round(v / (a.steps * PROGRAMS_PER_STEP), 4) for k, v in host_sum.items()}
 
     payload = s1["payload_bytes"] - s0["payload_bytes"]
     alg = s1["alg_bytes"] - s0["alg_bytes"]
     op_trace = (s1["acc_bytes"] - s0["acc_bytes"]) + (s1["store_bytes"] - s0["store_bytes"])
     total_payload = d.allsum(payload)
     value = total_payload / elapsed / 2**30
-
-    # Correctness of the run itself: finish the streams (lossless flush) and require that every
-    # original was received or recovered and no codec was disabled.
-    sess.finish()
-    fin = sess.summary()
-    ok = fin["missing_at_end"] == 0 and fin["disabled_codecs"] == 0
-    sess.close()
     all_ok = d.allsum(0.0 if ok else 1.0) == 0.0
 
     achieved = alg / (kernel_ms / 1e3) / 1e9 if kernel_ms > 0 else 0.0
     # Every rank's own figures (BASELINE.json configs[3]: per-GPU GiB/s beside the aggregate): its
     # payload over its own timed region, its executor's roofline fraction and busy share.
-    own_ms = (t1 - t0) * 1e3 / a.steps
-    per_rank = d.gather([float(rank), payload / (t1 - t0) / 2**30, achieved / HBM_PEAK_GBS,
-                         (kernel_ms / 1e3) / (t1 - t0), own_ms,
+    own_ms = own_s * 1e3 / a.steps
+    per_rank = d.gather([float(rank), payload / own_s / 2**30, achieved / HBM_PEAK_GBS,
+                         (kernel_ms / 1e3) / own_s, own_ms,
                          kernel_ms * 1e3 / launches if launches else 0.0])
-    pmc = pmc_traffic(a.workload, a.steps, a.warmup) if (rank == 0 and world == 1 and not a.no_pmc) else None
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, {"summary_timed": [s1[k] for k in DUMP_FIELDS],
+                                      "summary_timed_delta": [s1[k] - s0[k] for k in DUMP_FIELDS],
+                                      "summary_finished": [fin[k] for k in DUMP_FIELDS],
+                                      "record_transcript_sha256": record_digests(threads, device, loss,
+                                                                                 stream_base(rank))}, rank)
+    pmc = pmc_traffic(a.workload, a.steps, a.warmup) if (rank == 0 and world == 1 and a.full and not a.no_pmc) else None
     traffic = pmc.get("traffic_per_timed_launch") if pmc else None
     workload = {
         "cfg3": "configs[3] per-GPU shard: 64 independent streams/GPU, 65536 originals per stream per step " f"({PROGRAMS_PER_STEP} programs), "
@@ -866,6 +974,7 @@ def main() -> int:
             "workload": workload,
             "streams_per_gpu": STREAMS_PER_GPU, "originals_per_step": ORIGINALS_PER_STEP * PROGRAMS_PER_STEP,
             "originals_per_program": ORIGINALS_PER_STEP, "payload_bytes": PAYLOAD, "input_pool_per_stream": pool,
+            "sessions": len(plan), "warmup_steps_per_session": warm,
             "loss": loss, "ack_every": ACK, "host_threads_per_gpu": len(sess_cpus) or threads,
             "parallelism": f"streams sharded {STREAMS_PER_GPU}/GPU x {world} GPU, no collective",
             # each rank's pinned worker cores (its share of its GPU's NUMA node, tamd_cpu_share)
@@ -892,7 +1001,7 @@ def main() -> int:
             # op-trace bytes (every row an instruction reads or writes): the
             # gap to alg_bytes is what L2 / Infinity Cache serve
             "op_trace_bytes_per_launch": round(op_trace / launches, 1) if launches else None,
-            "device_busy_frac": round((kernel_ms / 1e3) / (t1 - t0), 4),
+            "device_busy_frac": round((kernel_ms / 1e3) / own_s, 4),
             # (placement diagnostics: the executor's launch time differs between processes)
             "arena": {"base": hex(arena_base), "bytes": arena_bytes, "base_mod_1g": arena_base % (1 << 30)},
             # (with several ranks this object is rank 0's executor; per_gpu holds every rank's)
@@ -907,11 +1016,12 @@ def main() -> int:
     }
     # The CPU leg runs after every rank's timed region: the reference codec on the host cores the
     # job owns (16 per GPU, so N x 16 at N GPUs, capped by this process's CPU set).
-    if rank == 0 and not a.no_cpu_baseline:
-        out["cpu_baseline"] = cpu_baseline(min(host_cpus(), threads * local_world), n_orig)
-    if rank == 0 and world == 1 and not a.no_end_to_end:
+    if rank == 0 and a.full and not a.no_cpu_baseline:
+        out["cpu_baseline"] = cpu_baseline(min(host_cpus(), threads * local_world),
+                                           (warm + plan[0]) * ORIGINALS_PER_STEP * PROGRAMS_PER_STEP)
+    if rank == 0 and world == 1 and a.full and not a.no_end_to_end:
         out["end_to_end"] = end_to_end(threads, device, loss)
-    if rank == 0 and a.workload == "cfg3" and not a.no_verify:
+    if rank == 0 and a.workload == "cfg3" and a.full and not a.no_verify:
         v = verify_schedule(threads, device)
         out["checks"]["digests_match"] = v["digests_match"]
         out["checks"]["verify"] = v

@@ -18,6 +18,6 @@ for rep in $(seq 1 $REPS); do
   for v in "$@"; do
     name=${v%%:*}; rest=${v#*:}; lib=${rest%%:*}; spec=${rest#*:}; [ "$spec" = "$rest" ] && spec=""
     e=""; [ "$lib" != "-" ] && e="TONK_AMD_LIB=$lib"
-    env $e ${spec//,/ } timeout -k 10 180 python bench.py --no-cpu-baseline --no-end-to-end --steps 30 ${BENCH_ARGS} > "$OUT/${TAG}_${name}_$rep.json" 2> "$OUT/${TAG}_${name}_$rep.err" || exit 1
+    env $e ${spec//,/ } timeout -k 10 180 python bench.py --full --no-cpu-baseline --no-end-to-end --steps 30 ${BENCH_ARGS} > "$OUT/${TAG}_${name}_$rep.json" 2> "$OUT/${TAG}_${name}_$rep.err" || exit 1
   done
 done

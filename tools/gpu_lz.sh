@@ -8,7 +8,7 @@ OUT=$R/gpurun_out
 TAG=${1:-lz}
 mkdir -p "$OUT" && cd "$R" &&
 timeout -k 10 300 python -u -m pytest tests/test_compress.py -m gpu -x -v --timeout 120 --timeout-method thread > "$OUT/${TAG}_tests.log" 2>&1 &&
-timeout -k 10 300 python bench.py --workload compress > "$OUT/${TAG}_bench_compress.json" 2> "$OUT/${TAG}_bench_compress.err" &&
+timeout -k 10 300 python bench.py --workload compress --full > "$OUT/${TAG}_bench_compress.json" 2> "$OUT/${TAG}_bench_compress.err" &&
 cd /tmp && export TMPDIR=/tmp &&
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof" -o run -- python3 "$R/bench.py" --workload compress --no-cpu-baseline > "$OUT/${TAG}_bench_compress_prof.json" 2> "$OUT/${TAG}_bench_compress_prof.err" &&
 cd "$R" &&

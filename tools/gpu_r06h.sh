@@ -7,6 +7,6 @@ OUT=$R/gpurun_out
 TAG=${1:-r06h}
 mkdir -p "$OUT" && cd "$R" &&
 timeout -k 10 300 python -u -m pytest tests/test_compress.py -m gpu -x -v --timeout 300 --timeout-method thread > "$OUT/${TAG}_lz_tests.log" 2>&1 &&
-timeout -k 10 300 python bench.py --workload compress > "$OUT/${TAG}_bench_compress.json" 2> "$OUT/${TAG}_bench_compress.err" &&
+timeout -k 10 300 python bench.py --workload compress --full > "$OUT/${TAG}_bench_compress.json" 2> "$OUT/${TAG}_bench_compress.err" &&
 TONK_AMD_LZ_PROF=1 timeout -k 10 300 python bench.py --workload compress --no-cpu-baseline > "$OUT/${TAG}_bench_compress_lzprof.json" 2> "$OUT/${TAG}_bench_compress_lzprof.err" &&
 timeout -k 10 90 tools/probe/bar_coherence > "$OUT/${TAG}_bar_coherence.txt" 2>&1

@@ -14,6 +14,6 @@ for v in "8 16 TONK_AMD_CAPI_BAR=0" "8 16 TONK_AMD_CAPI_BAR=1" "8 16 TONK_AMD_CA
 done
 } > "$OUT/${TAG}_bar_matrix.txt" 2>&1 &&
 timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "capi" --timeout 300 --timeout-method thread > "$OUT/${TAG}_capi_tests.log" 2>&1 &&
-for i in 1 2; do for b in 7 0; do TONK_AMD_CAPI_BAR=$b timeout -k 10 300 python bench.py --workload capi > "$OUT/${TAG}_capi_bar${b}_$i.json" 2> "$OUT/${TAG}_capi_bar${b}_$i.err" || exit 1; done; done &&
-for b in 7 0; do TONK_AMD_CAPI_WATCH=100 TONK_AMD_CAPI_BAR=$b timeout -k 10 300 python bench.py --workload capi > "$OUT/${TAG}_capi_watch_bar$b.json" 2> "$OUT/${TAG}_capi_watch_bar$b.err" || exit 1; done &&
+for i in 1 2; do for b in 7 0; do TONK_AMD_CAPI_BAR=$b timeout -k 10 300 python bench.py --workload capi --full > "$OUT/${TAG}_capi_bar${b}_$i.json" 2> "$OUT/${TAG}_capi_bar${b}_$i.err" || exit 1; done; done &&
+for b in 7 0; do TONK_AMD_CAPI_WATCH=100 TONK_AMD_CAPI_BAR=$b timeout -k 10 300 python bench.py --workload capi --full > "$OUT/${TAG}_capi_watch_bar$b.json" 2> "$OUT/${TAG}_capi_watch_bar$b.err" || exit 1; done &&
 REPS=1 bash tools/gpu_tonk_rep.sh ${TAG}bar

@@ -17,23 +17,23 @@ mkdir -p "$OUT" && cd "$R" || exit 1
 if [[ $PART == *a* ]]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 600 --timeout-method thread > "$OUT/gpu_tests_$TAG.log" 2>&1 &&
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_$TAG.log" 2>&1 &&
-  timeout -k 10 900 python bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || exit 1
+  timeout -k 10 900 python bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || exit 1
 fi
 if [[ $PART == *d* ]]; then
   timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_$TAG.log" 2>&1 &&
-  timeout -k 10 900 python bench.py > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || exit 1
+  timeout -k 10 900 python bench.py --full > "$OUT/bench_$TAG.json" 2> "$OUT/bench_$TAG.err" || exit 1
 fi
 if [[ $PART == *b* ]]; then
-  timeout -k 10 600 python bench.py --workload cfg2 --no-cpu-baseline --no-end-to-end > "$OUT/bench_cfg2_$TAG.json" 2> "$OUT/bench_cfg2_$TAG.err" &&
-  timeout -k 10 300 python bench.py --workload cfg1 > "$OUT/bench_cfg1_$TAG.json" 2> "$OUT/bench_cfg1_$TAG.err" &&
-  timeout -k 10 300 python bench.py --workload cfg4 > "$OUT/bench_cfg4_$TAG.json" 2> "$OUT/bench_cfg4_$TAG.err" &&
-  timeout -k 10 300 python bench.py --workload compress > "$OUT/bench_compress_$TAG.json" 2> "$OUT/bench_compress_$TAG.err" &&
+  timeout -k 10 600 python bench.py --workload cfg2 --full --no-cpu-baseline --no-end-to-end > "$OUT/bench_cfg2_$TAG.json" 2> "$OUT/bench_cfg2_$TAG.err" &&
+  timeout -k 10 300 python bench.py --workload cfg1 --full > "$OUT/bench_cfg1_$TAG.json" 2> "$OUT/bench_cfg1_$TAG.err" &&
+  timeout -k 10 300 python bench.py --workload cfg4 --full > "$OUT/bench_cfg4_$TAG.json" 2> "$OUT/bench_cfg4_$TAG.err" &&
+  timeout -k 10 300 python bench.py --workload compress --full > "$OUT/bench_compress_$TAG.json" 2> "$OUT/bench_compress_$TAG.err" &&
   ( cd /tmp && export TMPDIR=/tmp &&
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o run -- python3 "$R/bench.py" --no-cpu-baseline --no-end-to-end --no-verify --no-pmc > "$OUT/bench_prof_$TAG.json" 2> "$OUT/bench_prof_$TAG.err" &&
     python3 "$R/tools/trace_region.py" "$OUT/prof_$TAG/run_kernel_trace.csv" > "$OUT/trace_region_$TAG.json" &&
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_lz_$TAG" -o run -- python3 "$R/bench.py" --workload compress --no-cpu-baseline > "$OUT/bench_compress_prof_$TAG.json" 2> "$OUT/bench_compress_prof_$TAG.err" ) || exit 1
 fi
 if [[ $PART == *c* ]]; then
-  timeout -k 10 400 python bench.py --workload capi > "$OUT/bench_capi_$TAG.json" 2> "$OUT/bench_capi_$TAG.err" &&
+  timeout -k 10 400 python bench.py --workload capi --full > "$OUT/bench_capi_$TAG.json" 2> "$OUT/bench_capi_$TAG.err" &&
   bash tools/gpu_multi_rehearsal.sh || exit 1
 fi

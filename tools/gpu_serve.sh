@@ -21,5 +21,5 @@ PY
 timeout -k 10 600 python -u -m pytest tests/test_gpu_parity.py -k capi -x -v --timeout 120 --timeout-method thread \
     > "$OUT/${TAG}_capi_tests.log" 2>&1 || { echo "capi tests failed"; tail -30 "$OUT/${TAG}_capi_tests.log"; exit 1; }
 tail -3 "$OUT/${TAG}_capi_tests.log"
-timeout -k 10 300 python bench.py --workload capi > "$OUT/${TAG}_bench_capi.json" 2> "$OUT/${TAG}_bench_capi.err" || { echo "capi bench failed"; tail -5 "$OUT/${TAG}_bench_capi.err"; exit 1; }
+timeout -k 10 300 python bench.py --workload capi --full > "$OUT/${TAG}_bench_capi.json" 2> "$OUT/${TAG}_bench_capi.err" || { echo "capi bench failed"; tail -5 "$OUT/${TAG}_bench_capi.err"; exit 1; }
 cat "$OUT/${TAG}_bench_capi.json"

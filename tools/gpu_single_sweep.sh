@@ -7,7 +7,7 @@ for st in $steps; do
   for cfg in "$@"; do
     envs=(); [ "$cfg" != "-" ] && IFS=',' read -ra envs <<< "$cfg"
     f="$OUT/${TAG}_${w}_${st}_$(echo "$cfg" | tr -c 'A-Za-z0-9_\n' '_').json"
-    env "${envs[@]}" timeout -k 10 300 python bench.py --workload $w --step $st > "$f" 2> "$f.err" || { echo "$w $st $cfg failed"; tail -5 "$f.err"; exit 1; }
+    env "${envs[@]}" timeout -k 10 300 python bench.py --workload $w --step $st --full > "$f" 2> "$f.err" || { echo "$w $st $cfg failed"; tail -5 "$f.err"; exit 1; }
     python3 -c "
 import json,sys
 d=json.load(open(sys.argv[1])); p=d['per_program']; h=p['host_us_per_program']

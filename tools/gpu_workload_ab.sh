@@ -7,7 +7,7 @@ for r in $(seq 1 ${ROUNDS:-2}); do
   for cfg in "$@"; do
     envs=(); [ "$cfg" != "-" ] && IFS=',' read -ra envs <<< "$cfg"
     f="$OUT/${TAG}_${w}_${r}_$(echo "$cfg" | tr -c 'A-Za-z0-9_\n' '_').json"
-    env "${envs[@]}" timeout -k 10 400 python bench.py --workload $w > "$f" 2> "$f.err" || { echo "$cfg failed"; tail -5 "$f.err"; exit 1; }
+    env "${envs[@]}" timeout -k 10 400 python bench.py --workload $w --full > "$f" 2> "$f.err" || { echo "$cfg failed"; tail -5 "$f.err"; exit 1; }
     python3 -c "
 import json,sys
 d=json.load(open(sys.argv[1])); c=d.get('capi') or {}

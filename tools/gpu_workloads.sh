@@ -3,7 +3,7 @@
 # ABI and compression; one JSON line each under gpurun_out/<tag>_<workload>.json.
 R=${GRAFT_REPO_ROOT:-$PWD}; OUT=$R/gpurun_out; TAG=${1:-w}; shift; mkdir -p "$OUT"; cd "$R" || exit 1
 for w in ${@:-cfg2 cfg1 cfg4 capi}; do
-  timeout -k 10 400 python bench.py --workload $w > "$OUT/${TAG}_$w.json" 2> "$OUT/${TAG}_$w.err" || { echo "$w failed"; tail -5 "$OUT/${TAG}_$w.err"; exit 1; }
+  timeout -k 10 400 python bench.py --workload $w --full > "$OUT/${TAG}_$w.json" 2> "$OUT/${TAG}_$w.err" || { echo "$w failed"; tail -5 "$OUT/${TAG}_$w.err"; exit 1; }
   python3 -c "
 import json,sys
 d=json.load(open(sys.argv[1])); r=d.get('roofline') or {}; c=d.get('cpu_baseline') or {}
