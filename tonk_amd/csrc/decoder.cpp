@@ -1192,6 +1192,7 @@ Result Decoder::decode_checked_region() {
 // Decoder::EliminateOriginalData (:812-1063)
 bool Decoder::eliminate_original_data() {
     const uint32_t rows = cr_.recovery_count;
+    drun_valid_ = false;  // (eliminate_direct's range records: good for this solve only)
     for (uint32_t ri = 0; ri < rows; ++ri) {
         if (!mrows_[ri].used) continue;
         Recovery* rec = mrows_[ri].rec;
@@ -1324,55 +1325,64 @@ bool Decoder::eliminate_direct(Recovery* rec, uint32_t sum_elem, Sym& buf) {
     if (ee <= sum_elem || ee - sum_elem > Encoder::kDirectMax || ee > count_) return false;
     TAMD_PROF_SCOPE(kElimSums);
     const uint32_t rbytes = rec->bytes;
-    // the range's records: runs of segment packets and single known elements
-    drun_.clear();
-    uint32_t singles = 0;
-    for (uint32_t j = sum_elem; j < ee;) {
-        const uint32_t id = seg_id(j);
-        if (id != kSingle) {
-            const Segment& sg = segs_[id - seg_base_];
-            const uint32_t k = j + base_ - sg.first;
-            const uint32_t stop = std::min(sg.end() - base_, ee);
-            if (sg.bytes) drun_.push_back(DirectRun{j, stop - j, sg.off(k), sg.stride, std::min(sg.bytes, rbytes),
-                                                    col_add(sg.column0, k), kNoRow});
-            j = stop;
-            continue;
-        }
-        const StoredOriginal& o = elem(j);
-        if (o.bytes > 0) {
-            drun_.push_back(DirectRun{j, 0, 0, 0, std::min(o.bytes, rbytes), to_column(j), o.row});
-            ++singles;
-        }
-        ++j;
-    }
-    if (drun_.size() * Encoder::kDirectMinRun > ee - sum_elem) {
+    // The range's records: runs of segment packets and single known elements.  The rows of one
+    // solve mostly share their sums' start, so their ranges are nested: the list built for the
+    // longest is kept (eliminate_original_data drops it on entry: the window does not change
+    // inside a solve) and clipped to each row's end.
+    if (!drun_valid_ || drun_start_ != sum_elem || drun_end_ < ee) {
         drun_.clear();
-        return false;
+        for (uint32_t j = sum_elem; j < ee;) {
+            const uint32_t id = seg_id(j);
+            if (id != kSingle) {
+                const Segment& sg = segs_[id - seg_base_];
+                const uint32_t k = j + base_ - sg.first;
+                const uint32_t stop = std::min(sg.end() - base_, ee);
+                if (sg.bytes) drun_.push_back(DirectRun{j, stop - j, sg.off(k), sg.stride, sg.bytes,
+                                                        col_add(sg.column0, k), kNoRow});
+                j = stop;
+                continue;
+            }
+            const StoredOriginal& o = elem(j);
+            if (o.bytes > 0) drun_.push_back(DirectRun{j, 0, 0, 0, o.bytes, to_column(j), o.row});
+            ++j;
+        }
+        drun_valid_ = true;
+        drun_start_ = sum_elem;
+        drun_end_ = ee;
     }
-    // LDPC pairs (element << 8 | coefficient): those on a run's packets become its ADJ additions
-    // (sorted), the others are read as rows (only when the element has data).  The pairs span the
-    // row's whole unacknowledged window, mostly wider than the sum range: the ones outside it are
-    // read right away and only the rest are sorted.
+    size_t nrec = drun_.size();
+    while (nrec && drun_[nrec - 1].e0 >= ee) --nrec;
+    if (nrec * Encoder::kDirectMinRun > ee - sum_elem) return false;
+    // the runs as the emitter takes them, relative to sum_elem and clipped to this row
+    druns_.clear();
+    for (size_t i = 0; i < nrec; ++i) {
+        const DirectRun& r = drun_[i];
+        if (r.n) druns_.push_back(DenseRun{r.off, r.stride, std::min(r.n, ee - r.e0), std::min(r.len, rbytes), r.col,
+                                           r.e0 - sum_elem});
+    }
+    // LDPC pairs: those on a run's packets become its ADJ additions, the others are read as rows
+    // (only when the element has data).  The pairs span the row's whole unacknowledged window,
+    // mostly wider than the sum range: the ones outside it are read right away, in draw order, the
+    // rest as the walk below passes them.
     const uint8_t rx = row_value(m.Row);
     auto loose_pair = [&](uint64_t pr) {
         RowId row;
         uint32_t b;
         if (packet((uint32_t)(pr >> 8), row, b)) read_original(row, b < rbytes ? b : rbytes, (uint8_t)pr, buf);
     };
-    Pcg32 prng;
-    prng.seed(m.Row, m.LDPCCount);
-    const uint32_t pairs = (m.LDPCCount + kPairRate - 1) / kPairRate;
-    const FastMod ldpc_mod(m.LDPCCount);
-    const uint32_t span0 = drun_.empty() ? 0u : drun_.front().e0;
-    const uint32_t span1 = drun_.empty() ? 0u : drun_.back().e0 + (drun_.back().n ? drun_.back().n : 1u);
-    dpairs_.clear();
-    for (uint32_t i = 0; i < 2 * pairs; ++i) {
-        const uint64_t pr = (uint64_t)(es + ldpc_mod(prng.next())) << 8 | (i & 1u ? rx : 1u);
-        const uint32_t e = (uint32_t)(pr >> 8);
-        if (e >= span0 && e < span1) dpairs_.push_back(pr);
-        else loose_pair(pr);
+    draw_dense_pairs(m.Row, m.LDPCCount, rx, es - sum_elem, sum_elem, druns_.data(), druns_.size(), dkeys_, dpairs_);
+    const uint32_t span0 = nrec ? drun_[0].e0 : 0u;
+    const uint32_t span1 = nrec ? drun_[nrec - 1].e0 + (drun_[nrec - 1].n ? std::min(drun_[nrec - 1].n, ee - drun_[nrec - 1].e0) : 1u) : 0u;
+    {
+        size_t keep = 0;
+        for (uint64_t pr : dpairs_) {
+            const uint32_t e = (uint32_t)(pr >> 8);
+            if (e >= span0 && e < span1) dpairs_[keep++] = pr;
+            else loose_pair(pr);
+        }
+        dpairs_.resize(keep);
+        sort_pair_keys(dpairs_);
     }
-    std::sort(dpairs_.begin(), dpairs_.end());
     uint64_t ops = 0;
     uint8_t lk[kLanes][3];
     for (unsigned l = 0; l < kLanes; ++l) {
@@ -1388,50 +1398,45 @@ bool Decoder::eliminate_direct(Recovery* rec, uint32_t sum_elem, Sym& buf) {
     const uint32_t split = split_env >= 0 && ctx_->dense_split ? (uint32_t)split_env : ctx_->dense_split;
     const bool chunked = split && ee - sum_elem > split;
     ProgramBuilder& pb = ctx_->pb;
+    // The walk fixes the order of the row's terms (and allocates the chunks' partial rows, in
+    // chunk order); the chunk ops themselves are emitted after it, all at once.
+    if (chunked) dparts_.assign((ee - sum_elem + split - 1) / split, kNoRow);
     uint32_t chunk = ~0u;
-    RowId part = kNoRow;
-    auto close_chunk = [&]() {
-        if (part == kNoRow) return;
-        pb.finish_combine(part, rbytes, nullptr, 0);
-        buf.push_back(Term{part, rbytes, 1});
-        part = kNoRow;
-    };
-    size_t pi = 0;
-    for (const DirectRun& r : drun_) {
+    size_t pi = 0, ki = 0;
+    for (size_t i = 0; i < nrec; ++i) {
+        const DirectRun& r = drun_[i];
         while (pi < dpairs_.size() && (uint32_t)(dpairs_[pi] >> 8) < r.e0) loose_pair(dpairs_[pi++]);
         if (!r.n) {  // a single known element: its dense coefficient on the host
             const uint8_t* k = lk[r.col % kLanes];
             const uint8_t cx = column_value(r.col);
             const uint8_t c = (uint8_t)(k[0] ^ gf_mul(k[1], cx) ^ gf_mul(k[2], gf_sqr(cx)));
-            if (c) read_original(r.row, r.len, c, buf);
+            if (c) read_original(r.row, std::min(r.len, rbytes), c, buf);
             continue;
         }
-        for (uint32_t a = r.e0, end = r.e0 + r.n; a < end;) {
-            const uint32_t c = chunked ? (a - sum_elem) / split : 0u;
-            const uint32_t b = chunked ? std::min(end, sum_elem + (c + 1) * split) : end;
-            dadj_.clear();
-            for (; pi < dpairs_.size() && (uint32_t)(dpairs_[pi] >> 8) < b; ++pi)
-                dadj_.push_back(((uint32_t)(dpairs_[pi] >> 8) - a) << 16 | (uint32_t)(dpairs_[pi] & 0xffu) << 8);
-            const uint32_t off = r.off + (a - r.e0) * r.stride, col = col_add(r.col, a - r.e0);
-            if (!chunked) {
-                buf.push_back(pb.dense_run_term(off, r.stride, b - a, col, ops, rx, dadj_.data(),
-                                                (uint32_t)dadj_.size(), r.len));
-            } else {
-                if (c != chunk) {
-                    close_chunk();
-                    part = ctx_->alloc_temp(rbytes);
-                    if (part == kNoRow) return true;  // (ctx_->oom: the caller disables the decoder)
-                    chunk = c;
-                    pb.begin_op();
-                }
-                pb.op_accr_dense(off, r.stride, b - a, r.len, col, ops, rx, dadj_.data(), (uint32_t)dadj_.size());
-            }
-            a = b;
+        const uint32_t a = r.e0 - sum_elem, end = a + std::min(r.n, ee - r.e0);
+        if (!chunked) {
+            const size_t k0 = ki;
+            while (ki < dkeys_.size() && (dkeys_[ki] >> 8) < end) ++ki;
+            buf.push_back(pb.dense_run_term(r.off, r.stride, end - a, r.col, ops, rx, dkeys_.data() + k0,
+                                            (uint32_t)(ki - k0), a, std::min(r.len, rbytes)));
+            continue;
+        }
+        for (uint32_t c = a / split; c * split < end; ++c) {
+            if (c == chunk) continue;
+            if (chunk != ~0u) buf.push_back(Term{dparts_[chunk], rbytes, 1});
+            const RowId part = ctx_->alloc_temp(rbytes);
+            if (part == kNoRow) return true;  // (ctx_->oom: the caller disables the decoder)
+            dparts_[c] = part;
+            chunk = c;
         }
     }
-    close_chunk();
+    if (chunk != ~0u) {
+        buf.push_back(Term{dparts_[chunk], rbytes, 1});
+        const ProgramBuilder::DenseTarget t{ops, rx, ee - sum_elem, dkeys_.data(), (uint32_t)dkeys_.size(), kNoRow,
+                                            dparts_.data(), (uint32_t)dparts_.size(), nullptr, 0, nullptr, 0};
+        pb.emit_dense_range(druns_.data(), druns_.size(), &t, 1, split, rbytes, true);
+    }
     while (pi < dpairs_.size()) loose_pair(dpairs_[pi++]);
-    (void)singles;
     return true;
 }
 

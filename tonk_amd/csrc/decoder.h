@@ -260,10 +260,15 @@ private:
     Result decode_checked_region();
     bool eliminate_original_data();
     bool eliminate_direct(Recovery* rec, uint32_t sum_elem, Sym& buf);
+    // (len: the packets' own bytes, clipped to each row's length where it is read)
     struct DirectRun { uint32_t e0, n, off, stride, len, col; RowId row; };  // n 0: a single element
-    std::vector<DirectRun> drun_;
-    std::vector<uint64_t> dpairs_;
-    std::vector<uint32_t> dadj_;
+    std::vector<DirectRun> drun_;  // records of [drun_start_, drun_end_), kept over the rows of one solve
+    bool drun_valid_ = false;
+    uint32_t drun_start_ = 0, drun_end_ = 0;
+    std::vector<DenseRun> druns_;   // the row's runs, as ProgramBuilder::emit_dense_range takes them
+    std::vector<uint32_t> dkeys_;   // its pair entries on those runs
+    std::vector<uint64_t> dpairs_;  // and the others inside the records' span, by element
+    std::vector<RowId> dparts_;     // partial-sum rows by chunk (kNoRow: no packet in the chunk)
     bool multiply_lower_triangle();
     Result back_substitution();
     Result back_substitution_one();

@@ -799,7 +799,7 @@ void Encoder::add_dense(uint32_t row, uint32_t recovery_bytes, Sym& rec) {
 // (program.h), each packet weighted by its lane's opcode combination -- no lane walk, snapshot
 // or carried sum.  Bytes are the same: a lane sum is its packets zero-padded to the longest, and
 // each packet is clipped to the recovery length as the sum would be.  The row's LDPC pair
-// columns (light_pairs) are folded into the runs' coefficients (ADJ words); a pair column no run
+// columns (draw_dense_pairs) are folded into the runs' coefficients (ADJ words); a pair column no run
 // covers is read as a row of its own.
 //
 // Rows are queued (dgrp_) and emitted by emit_dense_group: rows of one sum range share its
@@ -842,17 +842,18 @@ bool Encoder::defer_dense(uint32_t row, uint32_t recovery_bytes, const RecoveryO
     t.hi = hi - lo;
     t.flen = out.footer_len;
     memcpy(t.footer, out.footer, sizeof(t.footer));
-    // pair columns as (element - lo) << 8 | coefficient: those inside a run stay (ADJ words),
-    // the others are resolved to their rows now (the window may have moved on by emission)
-    t.pairs.clear();
-    t.loose.clear();
-    size_t ri = 0;
-    for (uint64_t pr : pairs_) {
-        const uint32_t e = (uint32_t)(pr >> 8), rel = e - lo;
-        while (ri < runs.size() && runs[ri].e0 + runs[ri].count <= rel) ++ri;
-        if (rel < t.hi && ri < runs.size() && runs[ri].e0 <= rel) {
-            t.pairs.push_back((uint64_t)rel << 8 | (pr & 0xffu));
-        } else {
+    // The LDPC pair columns (AddLightColumns over the unacknowledged window): those on a run's
+    // packet stay entries of the row (ADJ words), the others -- placeholders, elements outside
+    // the range -- are resolved to their rows now (the window may have moved on by emission)
+    {
+        TAMD_PROF_SCOPE(kEncLight);
+        const uint32_t start = base_ + first_unremoved_;
+        draw_dense_pairs(row, sum_end_ - first_unremoved_, t.rx, start - lo, lo, runs.data(), runs.size(), t.pairs,
+                         pairs_);
+        sort_pair_keys(pairs_);
+        t.loose.clear();
+        for (uint64_t pr : pairs_) {
+            const uint32_t e = (uint32_t)(pr >> 8);
             const Segment& sg = seg_of(e - base_);
             t.loose.push_back(Term{sg.row(e - sg.first), sg.bytes, (uint8_t)(pr & 0xffu)});
         }
@@ -875,72 +876,14 @@ void Encoder::emit_dense_group() {
     const uint32_t n = dgrp_n_;
     if (!n) return;
     dgrp_n_ = 0;
-    ProgramBuilder& pb = ctx_->pb;
-    const uint32_t len = dgrp_len_, split = ctx_->dense_split;
-    const uint32_t total = dgrp_[n - 1].hi;  // the last (longest) range, relative to lo
-    const uint32_t step = split ? split : ~0u;
-    const uint32_t chunks = split && total > split ? (total + split - 1) / split : 1u;
-    const std::vector<DenseRun>& runs = dgrp_runs_;
-    size_t pc[3] = {0, 0, 0};  // per target: its next pair column
-    thread_local std::vector<uint32_t> adj[3];
-    size_t ri = 0;
-    for (uint32_t c = 0; c < chunks; ++c) {
-        const uint32_t c0 = c * step, c1 = total - c0 > step ? c0 + step : total;
-        uint32_t a0 = 0;  // targets a0 .. n-1 reach into this chunk (ranges are nested)
-        while (a0 < n && dgrp_[a0].hi <= c0) ++a0;
-        if (a0 == n) a0 = n - 1;  // (empty ranges: the stores still run)
-        const uint32_t nt = n - a0;
-        pb.begin_op();
-        for (; ri < runs.size() && runs[ri].e0 < c1; ++ri) {
-            const DenseRun& r = runs[ri];
-            const uint32_t pa = r.e0 > c0 ? r.e0 : c0, pe = r.e0 + r.count < c1 ? r.e0 + r.count : c1;
-            const uint32_t k = pe - pa;
-            ProgramBuilder::DenseCoefs tc[3];
-            for (uint32_t t = 0; t < nt; ++t) {
-                const DenseTarget& d = dgrp_[a0 + t];
-                const uint32_t h = d.hi > pa ? (d.hi - pa < k ? d.hi - pa : k) : 0u;
-                adj[t].clear();
-                while (pc[a0 + t] < d.pairs.size() && (uint32_t)(d.pairs[pc[a0 + t]] >> 8) < pa + h) {
-                    const uint64_t pr = d.pairs[pc[a0 + t]++];
-                    adj[t].push_back(((uint32_t)(pr >> 8) - pa) << 16 | (uint32_t)(pr & 0xffu) << 8);
-                }
-                tc[t] = ProgramBuilder::DenseCoefs{d.ops, d.rx, h, adj[t].data(), (uint32_t)adj[t].size()};
-            }
-            if (nt == 1) pb.op_accr_dense(r.off + (pa - r.e0) * r.stride, r.stride, k, r.len, col_add(r.col, pa - r.e0),
-                                          tc[0].ops, tc[0].rx, tc[0].adj, tc[0].nadj);
-            else pb.op_accr_dense_multi(r.off + (pa - r.e0) * r.stride, r.stride, k, r.len,
-                                        col_add(r.col, pa - r.e0), tc, nt);
-            if (pe < r.e0 + r.count) break;  // the run continues in the next chunk
-        }
-        // rows over one chunk are finished here (their loose pair columns included), the others
-        // store this chunk's partial sum
-        for (uint32_t t = 0; t < nt; ++t) {
-            const DenseTarget& d = dgrp_[a0 + t];
-            if (d.parts.empty())
-                for (const Term& x : d.loose) pb.op_acc(x.row, x.coef, x.len, t);
-        }
-        if (nt == 1) {
-            const DenseTarget& d = dgrp_[a0];
-            if (d.parts.empty()) pb.finish_combine(d.row, len, d.footer, d.flen);
-            else pb.finish_combine(d.parts[c], len, nullptr, 0);
-        } else {
-            for (uint32_t t = 0; t < nt; ++t) {
-                const DenseTarget& d = dgrp_[a0 + t];
-                if (d.parts.empty()) pb.op_store_shared(d.row, len, t, d.footer, d.flen);
-                else pb.op_store_shared(d.parts[c], len, t, nullptr, 0);
-            }
-            pb.end_op(1);
-        }
-    }
-    // rows over several chunks: their partial sums and loose pair columns (level 2)
+    ProgramBuilder::DenseTarget tg[3];
     for (uint32_t a = 0; a < n; ++a) {
         const DenseTarget& d = dgrp_[a];
-        if (d.parts.empty()) continue;
-        pb.begin_op();
-        for (RowId p : d.parts) pb.op_acc(p, 1, len);
-        for (const Term& x : d.loose) pb.op_acc(x.row, x.coef, x.len);
-        pb.finish_combine(d.row, len, d.footer, d.flen);
+        tg[a] = ProgramBuilder::DenseTarget{d.ops, d.rx, d.hi, d.pairs.data(), (uint32_t)d.pairs.size(), d.row,
+                                            d.parts.empty() ? nullptr : d.parts.data(), (uint32_t)d.parts.size(),
+                                            d.loose.data(), (uint32_t)d.loose.size(), d.footer, d.flen};
     }
+    ctx_->pb.emit_dense_range(dgrp_runs_.data(), dgrp_runs_.size(), tg, n, ctx_->dense_split, dgrp_len_, false);
 }
 
 // Encoder::AddLightColumns (SiameseEncoder.cpp:1100-1144).  The product half goes straight into
@@ -965,33 +908,6 @@ void Encoder::add_light(uint32_t row, Sym& rec) {
         const Segment& srx = seg_of(erx);
         t[2 * i] = Term{s1.row(e1 + base_ - s1.first), s1.bytes, 1};
         t[2 * i + 1] = Term{srx.row(erx + base_ - srx.first), srx.bytes, rx};
-    }
-}
-
-void Encoder::light_pairs(uint32_t row, std::vector<uint64_t>& out) {
-    const uint32_t start = first_unremoved_;
-    const uint32_t count = sum_end_ - start;
-    const uint8_t rx = row_value(row);
-    Pcg32 prng;
-    prng.seed(row, count);
-    const uint32_t pairs = (count + kPairRate - 1) / kPairRate;
-    out.resize(2 * (size_t)pairs);
-    const FastMod mod(count);
-    for (uint32_t i = 0; i < pairs; ++i) {
-        const uint32_t e1 = start + mod(prng.next());
-        const uint32_t erx = start + mod(prng.next());
-        out[2 * i] = (uint64_t)(base_ + e1) << 8 | 1u;
-        out[2 * i + 1] = (uint64_t)(base_ + erx) << 8 | rx;
-    }
-    // (a few dozen entries: insertion sort)
-    for (size_t i = 1; i < out.size(); ++i) {
-        const uint64_t x = out[i];
-        size_t j = i;
-        while (j > 0 && out[j - 1] > x) {
-            out[j] = out[j - 1];
-            --j;
-        }
-        out[j] = x;
     }
 }
 
@@ -1059,10 +975,9 @@ Result Encoder::encode(RecoveryOut& out) {
     } else {
         sum_end_ = count_;
     }
-    {
+    if (!direct) {  // (a direct row's pairs are drawn by defer_dense, into its runs' coefficients)
         TAMD_PROF_SCOPE(kEncLight);
-        if (direct) light_pairs(row, pairs_);  // (folded into the dense runs' coefficients)
-        else add_light(row, rec);
+        add_light(row, rec);
     }
 
     RecoveryMeta m;

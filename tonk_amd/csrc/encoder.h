@@ -268,9 +268,7 @@ private:
     bool direct_sums() const;  // a Siamese row reads its sum range straight from the packets
     void add_dense(uint32_t row, uint32_t recovery_bytes, Sym& rec);
     void add_light(uint32_t row, Sym& rec);
-    // The same pair columns as (absolute element << 8 | coefficient), sorted by element.
-    void light_pairs(uint32_t row, std::vector<uint64_t>& out);
-    std::vector<uint64_t> pairs_;
+    std::vector<uint64_t> pairs_;  // a direct row's pair columns off its runs (defer_dense scratch)
     Result emit(Sym& terms, uint32_t len, const RecoveryMeta& meta, RecoveryOut& out, bool distinct);
     Sym scratch_, rec_;
     struct Run { RowId row; uint32_t off, stride, count, len, col; };
@@ -301,14 +299,13 @@ private:
     // starts at the same element and ends at the window end of its encode, so the ranges are
     // nested and the last row's runs are their union: each packet is read once for the group
     // instead of once per row (a packet was read by ~4 rows on the headline workload).
-    struct DenseRun { uint32_t off, stride, count, len, col, e0; };  // e0: absolute first element
     struct DenseTarget {
         RowId row = kNoRow;
         uint64_t ops = 0;            // lane opcodes, 6 bits each
         uint32_t hi = 0, flen = 0;   // absolute end of the range; footer bytes
         uint8_t rx = 0;
         uint8_t footer[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        std::vector<uint64_t> pairs; // LDPC pair columns inside its runs: (element - lo) << 8 | coef
+        std::vector<uint32_t> pairs; // LDPC pair columns inside its runs: (element - lo) << 8 | coef
         Sym loose;                   // the others, as rows
         std::vector<RowId> parts;    // partial sums, one per chunk (ranges over one chunk: none)
     };

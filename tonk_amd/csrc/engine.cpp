@@ -133,6 +133,20 @@ void RowTable::release_up_to(uint64_t completed) {
 // ---------------------------------------------------------------------------------------------
 static void push_store(InstrVec& v, uint32_t off, uint32_t len, uint32_t cap,
                        const uint8_t* footer, uint32_t flen, uint32_t acc = 0);
+ProgramBuilder::ProgramBuilder(RowTable* rows) : rows_(rows) {
+    // (TONK_AMD_CLASS="rows_div,t1,t2,t3,rows0": A/B knob for the cost class thresholds of end_op)
+    if (const char* e = getenv("TONK_AMD_CLASS")) {
+        unsigned long long v[5] = {cls_div_, cls_t1_, cls_t2_, cls_t3_, cls_r0_};
+        sscanf(e, "%llu,%llu,%llu,%llu,%llu", &v[0], &v[1], &v[2], &v[3], &v[4]);
+        cls_div_ = v[0] ? v[0] : 2;
+        cls_t1_ = v[1];
+        cls_t2_ = v[2];
+        cls_t3_ = v[3];
+        cls_r0_ = v[4];
+    }
+}
+
+// (the vectors keep the capacity the previous programs reached: pushes do not allocate)
 void ProgramBuilder::clear() {
     ops_.clear();
     instrs_.clear();
@@ -224,32 +238,26 @@ void ProgramBuilder::op_accr_dense(uint32_t row0, uint32_t stride, uint32_t coun
                                    uint64_t ops, uint8_t rx, const uint32_t* adj, uint32_t nadj, uint8_t scale) {
     if (!len || !count || !scale) return;
     const uint32_t nwords = (nadj + 3) / 4;
-    tamd_instr a, r, g;
-    a.w0 = tamd_w0(TAMD_I_ACCR, TAMD_R_DENSE, 0) | (scale > 1 ? (uint32_t)scale << 24 : 0u);
-    a.row = row0;
-    a.len = len;
-    a.cap = count;
-    r.w0 = TAMD_I_RANGE;
-    r.row = stride;
-    r.len = col0;
-    r.cap = 1;
-    g.w0 = TAMD_I_COEFS;
-    g.row = (uint32_t)ops;
-    g.len = (uint32_t)(ops >> 32) & 0xffffu;
-    g.len |= (uint32_t)rx << 16;
-    g.cap = nwords;
-    instrs_.push_back(a);
-    instrs_.push_back(r);
-    instrs_.push_back(g);
-    for (uint32_t w = 0; w < nwords; ++w) {
-        uint32_t d[4] = {0, 0, 0, 0};
-        for (uint32_t q = 0; q < 4 && 4 * w + q < nadj; ++q) d[q] = adj[4 * w + q];
-        tamd_instr x;
-        x.w0 = (d[0] & ~0xffu) | TAMD_I_ADJ;
-        x.row = d[1];
-        x.len = d[2];
-        x.cap = d[3];
-        instrs_.push_back(x);
+    tamd_instr* w = reserve(3 + nwords);
+    w[0].w0 = tamd_w0(TAMD_I_ACCR, TAMD_R_DENSE, 0) | (scale > 1 ? (uint32_t)scale << 24 : 0u);
+    w[0].row = row0;
+    w[0].len = len;
+    w[0].cap = count;
+    w[1].w0 = TAMD_I_RANGE;
+    w[1].row = stride;
+    w[1].len = col0;
+    w[1].cap = 1;
+    w[2].w0 = TAMD_I_COEFS;
+    w[2].row = (uint32_t)ops;
+    w[2].len = ((uint32_t)(ops >> 32) & 0xffffu) | (uint32_t)rx << 16;
+    w[2].cap = nwords;
+    w += 3;
+    for (uint32_t q = 0; q < nadj; q += 4, ++w) {
+        const uint32_t m = nadj - q;
+        w->w0 = (adj[q] & ~0xffu) | TAMD_I_ADJ;
+        w->row = m > 1 ? adj[q + 1] : 0u;
+        w->len = m > 2 ? adj[q + 2] : 0u;
+        w->cap = m > 3 ? adj[q + 3] : 0u;
     }
     ++cur_runs_;  // (acc_0 only: the op stays a pure combine)
     if (len > cur_span_) cur_span_ = len;
@@ -257,44 +265,225 @@ void ProgramBuilder::op_accr_dense(uint32_t row0, uint32_t stride, uint32_t coun
     acc_bytes_ += (uint64_t)len * count;
 }
 
-void ProgramBuilder::op_accr_dense_multi(uint32_t row0, uint32_t stride, uint32_t count, uint32_t len,
-                                         uint32_t col0, const DenseCoefs* t, uint32_t nt) {
-    if (!len || !count || nt < 2 || nt > 3) return;
-    tamd_instr a, r;
-    a.w0 = tamd_w0(TAMD_I_ACCR, TAMD_R_DENSE, nt);
-    a.row = row0;
-    a.len = len;
-    a.cap = count;
-    r.w0 = TAMD_I_RANGE;
-    r.row = stride;
-    r.len = col0;
-    r.cap = 1;
-    instrs_.push_back(a);
-    instrs_.push_back(r);
-    for (uint32_t k = 0; k < nt; ++k) {
-        const uint32_t nwords = (t[k].nadj + 3) / 4;
-        tamd_instr g;
-        g.w0 = TAMD_I_COEFS;
-        g.row = (uint32_t)t[k].ops;
-        g.len = ((uint32_t)(t[k].ops >> 32) & 0xffffu) | (uint32_t)t[k].rx << 16;
-        g.cap = nwords | (t[k].hi < count ? t[k].hi : count) << 16;
-        instrs_.push_back(g);
-        for (uint32_t w = 0; w < nwords; ++w) {
-            uint32_t d[4] = {0, 0, 0, 0};
-            for (uint32_t q = 0; q < 4 && 4 * w + q < t[k].nadj; ++q) d[q] = t[k].adj[4 * w + q];
-            tamd_instr x;
-            x.w0 = (d[0] & ~0xffu) | TAMD_I_ADJ;
-            x.row = d[1];
-            x.len = d[2];
-            x.cap = d[3];
-            instrs_.push_back(x);
+// ---------------------------------------------------------------------------------------------
+// Siamese rows read straight from the packets
+// ---------------------------------------------------------------------------------------------
+void draw_dense_pairs(uint32_t row, uint32_t count, uint8_t rx, uint32_t first_rel, uint32_t origin,
+                      const DenseRun* runs, size_t nruns, std::vector<uint32_t>& in, std::vector<uint64_t>& loose) {
+    Pcg32 prng;
+    prng.seed(row, count);
+    const uint32_t pairs = (count + kPairRate - 1) / kPairRate;
+    const FastMod mod(count);
+    const uint32_t end = nruns ? runs[nruns - 1].e0 + runs[nruns - 1].count : 0u;
+    static const uint32_t kSmall = 64, kBits = 512, kBuckets = 16;
+    if (2 * pairs > kSmall || end > kBits) {  // (long windows, ranges past kDirectMax: no fixed-size scratch)
+        in.clear();
+        loose.clear();
+        for (uint32_t i = 0; i < 2 * pairs; ++i) {
+            const uint32_t rel = first_rel + mod(prng.next());
+            const uint32_t coef = i & 1u ? rx : 1u;
+            size_t r = 0;
+            while (r < nruns && rel - runs[r].e0 >= runs[r].count) ++r;
+            if (r < nruns) in.push_back(rel << 8 | coef);
+            else loose.push_back((uint64_t)(origin + rel) << 8 | coef);
         }
+        std::sort(in.begin(), in.end());
+        return;
     }
-    ++cur_runs_;
-    cur_multi_ = true;
-    if (len > cur_span_) cur_span_ = len;
-    if (len < cur_full_) cur_full_ = len;
-    acc_bytes_ += (uint64_t)len * count;
+    // The usual case.  The draws are random, so a branch on one is a misprediction: the runs'
+    // elements are a bitmap, an entry is written to both lists and only the cursor of its own
+    // moves.  Covered entries are then placed by blocks of 2^shift elements (counted as they are
+    // drawn; any monotone bucketing keeps the order) and ordered within a block, one or two each.
+    uint64_t bm[kBits / 64 + 1] = {0};
+    for (size_t r = 0; r < nruns; ++r)
+        for (uint32_t e = runs[r].e0, e1 = e + runs[r].count; e < e1;) {
+            const uint32_t w = e >> 6, b = e & 63u, n = std::min(64u - b, e1 - e);
+            bm[w] |= (n == 64 ? ~0ull : ((1ull << n) - 1)) << b;
+            e += n;
+        }
+    uint32_t shift = 4;
+    while ((end >> shift) >= kBuckets) ++shift;
+    uint8_t cnt[kBuckets + 2] = {0}, fill[kBuckets] = {0};
+    uint32_t keys[kSmall + 1];
+    uint64_t out[kSmall + 1];
+    uint32_t nk = 0, no = 0;
+    for (uint32_t i = 0; i < 2 * pairs; ++i) {
+        const uint32_t rel = first_rel + mod(prng.next());
+        const uint32_t coef = i & 1u ? rx : 1u;
+        const uint32_t at = rel < kBits ? rel : kBits;  // (bm's last word stays zero)
+        const uint32_t covered = (uint32_t)(bm[at >> 6] >> (at & 63u)) & 1u;
+        keys[nk] = rel << 8 | coef;
+        out[no] = (uint64_t)(origin + rel) << 8 | coef;
+        nk += covered;
+        no += covered ^ 1u;
+        cnt[covered ? (at >> shift) + 2 : 0] += (uint8_t)covered;
+    }
+    loose.assign(out, out + no);
+    in.resize(nk);
+    for (uint32_t b = 2; b < kBuckets + 2; ++b) cnt[b] = (uint8_t)(cnt[b] + cnt[b - 1]);  // cnt[b + 1]: where bucket b starts
+    uint32_t* const dst = in.data();
+    for (uint32_t i = 0; i < nk; ++i) {
+        const uint32_t key = keys[i], b = key >> (8 + shift);
+        uint32_t* p = dst + cnt[b + 1];
+        uint32_t j = fill[b]++;
+        for (; j > 0 && p[j - 1] > key; --j) p[j] = p[j - 1];
+        p[j] = key;
+    }
+}
+
+static inline tamd_instr* put_store(tamd_instr* w, uint32_t off, uint32_t len, uint32_t cap, const uint8_t* footer,
+                                    uint32_t flen, uint32_t acc) {
+    w[0].w0 = tamd_w0(TAMD_I_STORE, flen, acc);
+    w[0].row = off;
+    w[0].len = len;
+    w[0].cap = cap;
+    uint8_t fb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (flen) memcpy(fb, footer, flen);
+    w[1].w0 = tamd_w0(TAMD_I_FOOTER, 0);
+    memcpy(&w[1].row, fb, 4);
+    memcpy(&w[1].len, fb + 4, 4);
+    w[1].cap = 0;
+    return w + 2;
+}
+
+void ProgramBuilder::emit_dense_range(const DenseRun* runs, size_t nruns, const DenseTarget* tg, uint32_t n,
+                                      uint32_t split, uint32_t len, bool skip_empty) {
+    if (!n || n > 3) return;
+    const uint32_t total = tg[n - 1].hi;  // the last (longest) range
+    const uint32_t step = split ? split : ~0u;
+    const uint32_t chunks = split && total > split ? (total + split - 1) / split : 1u;
+    // every word the range can take: a chunk boundary cuts at most one run in two
+    size_t bound = (nruns + chunks) * (2 + n) + 2 * (size_t)n * chunks;
+    for (uint32_t a = 0; a < n; ++a) bound += tg[a].npairs + 2 * (size_t)tg[a].nloose + tg[a].nparts + 2;
+    tamd_instr* const base = reserve(bound);
+    tamd_instr* w = base;
+    const uint32_t base_index = (uint32_t)(base - instrs_.data());
+    uint32_t pc[3] = {0, 0, 0};  // per row: its next pair entry
+    // op bookkeeping shared by the chunk ops and the rows' own ops
+    uint32_t span = 0, full = ~0u, lvl = 0;
+    uint64_t acc = 0;
+    bool pure = true, multi = false;
+    auto open = [&]() {
+        cur_first_ = base_index + (uint32_t)(w - base);
+        cur_acc_begin_ = acc_bytes_;
+        cur_written_begin_ = written_.size();
+        cur_runs_ = 0;
+        span = 0, full = ~0u, lvl = 0, acc = 0;
+        pure = true, multi = false;
+    };
+    auto put_acc = [&](RowId src, uint8_t coef, uint32_t l, uint32_t a) {
+        if (!coef || !l) return;
+        if (a) pure = false;
+        w->w0 = tamd_w0(TAMD_I_ACC, coef, a);
+        w->row = rows_->offset(src);
+        w->len = l;
+        w->cap = 0;
+        ++w;
+        if (l > span) span = l;
+        if (l < full) full = l;
+        const uint32_t sl = rows_->level(src);
+        if (sl > lvl) lvl = sl;
+        acc += l;
+    };
+    auto store = [&](RowId dst, uint32_t a, const uint8_t* footer, uint32_t flen) {
+        const uint32_t cap = rows_->cap_bytes(dst);
+        w = put_store(w, rows_->offset(dst), len, cap, footer, flen, a);
+        if (a) multi = true;
+        if (cap > span) span = cap;
+        if (len > span) span = len;
+        if (len < full) full = len;
+        written_.push_back(dst);
+        store_bytes_ += len + flen;
+    };
+    auto close = [&]() {
+        cur_span_ = span;
+        cur_full_ = full;
+        cur_level_in_ = lvl;
+        cur_pure_ = pure;
+        cur_multi_ = multi;
+        acc_bytes_ += acc;
+        close_op(base_index + (uint32_t)(w - base), 1);
+    };
+    size_t ri = 0;
+    for (uint32_t c = 0; c < chunks; ++c) {
+        const uint32_t c0 = c * step, c1 = total - c0 > step ? c0 + step : total;
+        if (skip_empty && (ri >= nruns || runs[ri].e0 >= c1)) continue;
+        uint32_t a0 = 0;  // rows a0 .. n-1 reach into this chunk (ranges are nested)
+        while (a0 < n && tg[a0].hi <= c0) ++a0;
+        if (a0 == n) a0 = n - 1;  // (empty ranges: the stores still run)
+        const uint32_t nt = n - a0;
+        open();
+        for (; ri < nruns && runs[ri].e0 < c1; ++ri) {
+            const DenseRun& r = runs[ri];
+            const uint32_t pa = r.e0 > c0 ? r.e0 : c0, pe = r.e0 + r.count < c1 ? r.e0 + r.count : c1;
+            const uint32_t k = pe - pa;
+            tamd_instr* const head = w;
+            w[0].w0 = tamd_w0(TAMD_I_ACCR, TAMD_R_DENSE, nt > 1 ? nt : 0u);
+            w[0].row = r.off + (pa - r.e0) * r.stride;
+            w[0].len = r.len;
+            w[0].cap = k;
+            w[1].w0 = TAMD_I_RANGE;
+            w[1].row = r.stride;
+            w[1].len = col_add(r.col, pa - r.e0);
+            w[1].cap = 1;
+            w += 2;
+            for (uint32_t t = 0; t < nt; ++t) {
+                const DenseTarget& d = tg[a0 + t];
+                const uint32_t h = d.hi > pa ? (d.hi - pa < k ? d.hi - pa : k) : 0u;
+                tamd_instr* const g = w++;
+                uint32_t q = 0, p = pc[a0 + t];
+                for (; p < d.npairs && (d.pairs[p] >> 8) < pa + h; ++p, ++q) {
+                    const uint32_t v = ((d.pairs[p] >> 8) - pa) << 16 | (d.pairs[p] & 0xffu) << 8;
+                    switch (q & 3u) {
+                    case 0: w->w0 = v | TAMD_I_ADJ, w->row = 0, w->len = 0, w->cap = 0; break;
+                    case 1: w->row = v; break;
+                    case 2: w->len = v; break;
+                    default: w->cap = v, ++w; break;
+                    }
+                }
+                if (q & 3u) ++w;
+                pc[a0 + t] = p;
+                g->w0 = TAMD_I_COEFS;
+                g->row = (uint32_t)d.ops;
+                g->len = ((uint32_t)(d.ops >> 32) & 0xffffu) | (uint32_t)d.rx << 16;
+                g->cap = (q + 3) / 4 | (nt > 1 ? h << 16 : 0u);
+            }
+            if (!r.len || !k) {  // (nothing to read: only the pair cursors moved)
+                w = head;
+            } else {
+                ++cur_runs_;
+                if (nt > 1) multi = true;
+                if (r.len > span) span = r.len;
+                if (r.len < full) full = r.len;
+                acc += (uint64_t)r.len * k;
+            }
+            if (pe < r.e0 + r.count) break;  // the run continues in the next chunk
+        }
+        // rows over one chunk are finished here (their loose pair columns included), the others
+        // store this chunk's partial sum
+        for (uint32_t t = 0; t < nt; ++t) {
+            const DenseTarget& d = tg[a0 + t];
+            if (!d.parts)
+                for (uint32_t i = 0; i < d.nloose; ++i) put_acc(d.loose[i].row, d.loose[i].coef, d.loose[i].len, t);
+        }
+        for (uint32_t t = 0; t < nt; ++t) {
+            const DenseTarget& d = tg[a0 + t];
+            if (!d.parts) store(d.dst, t, d.footer, d.flen);
+            else store(d.parts[c], t, nullptr, 0);
+        }
+        close();
+    }
+    // rows over several chunks: their partial sums and loose pair columns (one level up)
+    for (uint32_t a = 0; a < n; ++a) {
+        const DenseTarget& d = tg[a];
+        if (!d.parts || d.dst == kNoRow) continue;
+        open();
+        for (uint32_t i = 0; i < d.nparts; ++i) put_acc(d.parts[i], 1, len, 0);
+        for (uint32_t i = 0; i < d.nloose; ++i) put_acc(d.loose[i].row, d.loose[i].coef, d.loose[i].len, 0);
+        store(d.dst, 0, d.footer, d.flen);
+        close();
+    }
+    commit(w);
 }
 
 void ProgramBuilder::op_store_shared(RowId dst, uint32_t len, uint32_t acc, const uint8_t* footer,
@@ -411,36 +600,21 @@ void ProgramBuilder::op_store(RowId dst, uint32_t len, uint32_t acc, const uint8
     store_bytes_ += len + footer_len;
 }
 
-uint32_t ProgramBuilder::end_op(uint32_t min_level) {
+uint32_t ProgramBuilder::close_op(uint32_t end, uint32_t min_level) {
     uint32_t level = cur_level_in_ + 1;
     if (level < min_level) level = min_level;
     tamd_op op;
     op.first = cur_first_;
-    op.count = (uint32_t)instrs_.size() - cur_first_;
+    op.count = end - cur_first_;
     op.span = (cur_span_ + 7u) & ~7u;
     op.full = cur_full_ < op.span ? cur_full_ : op.span;
     ops_.push_back(op);
     // Cost class from the op's length in the executor's terms: instructions, and row loads
     // (an ACCR run is `count` rows); class 0 is the most expensive and starts first.
-    // (TONK_AMD_CLASS="rows_div,t1,t2,t3,rows0": A/B knob for the thresholds, default 2,64,32,12,48)
-    struct ClassCfg {
-        uint64_t div = 2, t1 = 64, t2 = 32, t3 = 12, r0 = 48;
-        ClassCfg() {
-            if (const char* e = getenv("TONK_AMD_CLASS")) {
-                unsigned long long v[5] = {div, t1, t2, t3, r0};
-                sscanf(e, "%llu,%llu,%llu,%llu,%llu", &v[0], &v[1], &v[2], &v[3], &v[4]);
-                div = v[0] ? v[0] : 2;
-                t1 = v[1];
-                t2 = v[2];
-                t3 = v[3];
-                r0 = v[4];
-            }
-        }
-    };
-    static const ClassCfg cc;
     const uint64_t rows = (acc_bytes_ - cur_acc_begin_) / 1024u;
-    const uint64_t cost = op.count + 4u * cur_runs_ + rows / cc.div;
-    const uint32_t cls = (cur_pure_ && rows >= cc.r0) ? 0u : cost >= cc.t1 ? 1u : cost >= cc.t2 ? 2u : cost >= cc.t3 ? 3u : 4u;
+    const uint64_t cost = op.count + 4u * cur_runs_ + rows / cls_div_;
+    const uint32_t cls = (cur_pure_ && rows >= cls_r0_) ? 0u
+                         : cost >= cls_t1_ ? 1u : cost >= cls_t2_ ? 2u : cost >= cls_t3_ ? 3u : 4u;
     const uint32_t bucket = TAMD_COST_CLASSES * level + cls;
     levels_.push_back(bucket);
     pure_.push_back(cur_pure_ ? (cur_multi_ ? 2 : 1) : 0);

@@ -164,9 +164,42 @@ private:
 // ---------------------------------------------------------------------------------------------
 // Device program under construction.
 // ---------------------------------------------------------------------------------------------
+// A run of level-0 packets inside a Siamese row's sum range: rows off + k * stride (64-B units),
+// columns col + k, k < count, each read over len bytes; e0 is the run's first element counted from
+// the range's start.
+struct DenseRun { uint32_t off, stride, count, len, col, e0; };
+
+// The LDPC pair columns of Siamese row `row` over `count` elements (SiameseEncoder.cpp:1100-1144,
+// SiameseDecoder.cpp:1029-1047: the same PCG32 seed and draws, the same FastMod), drawn once into
+// the form ProgramBuilder::emit_dense_range consumes.  Draw i names element first_rel + draw mod
+// count, counted from the range's start (first_rel may be "negative": the pairs span the
+// unacknowledged window, the sums their own range), with coefficient 1 (even i) or rx (odd i).
+//   in:    entries on a packet of `runs`, as rel << 8 | coef in ascending order (they are bucketed by
+//          blocks of elements as they are drawn and ordered within a bucket: a handful each)
+//   loose: the others, as (uint64_t)(origin + rel) << 8 | coef in draw order
+void draw_dense_pairs(uint32_t row, uint32_t count, uint8_t rx, uint32_t first_rel, uint32_t origin,
+                      const DenseRun* runs, size_t nruns, std::vector<uint32_t>& in, std::vector<uint64_t>& loose);
+inline void sort_pair_keys(std::vector<uint64_t>& v) {  // (a few entries: insertion sort)
+    for (size_t i = 1; i < v.size(); ++i) {
+        const uint64_t x = v[i];
+        size_t j = i;
+        for (; j > 0 && v[j - 1] > x; --j) v[j] = v[j - 1];
+        v[j] = x;
+    }
+}
+
 class ProgramBuilder {
 public:
-    explicit ProgramBuilder(RowTable* rows) : rows_(rows) {}
+    explicit ProgramBuilder(RowTable* rows);
+
+    // Instruction space for up to n words at the end of the program: write them in place, then
+    // commit(end) keeps the words before `end`.  No other instruction is added in between.
+    tamd_instr* reserve(size_t n) {
+        const size_t at = instrs_.size();
+        instrs_.resize(at + n);
+        return instrs_.data() + at;
+    }
+    void commit(const tamd_instr* end) { instrs_.resize((size_t)(end - instrs_.data())); }
 
     // Emit `dst[0:len] = sum terms`, followed by `footer` (<= 8 bytes) and zero fill to the
     // row capacity.  Assigns and returns the op's level (also recorded on dst).
@@ -188,12 +221,33 @@ public:
     // coefficient additions (ADJ words).
     void op_accr_dense(uint32_t row0, uint32_t stride, uint32_t count, uint32_t len, uint32_t col0, uint64_t ops,
                        uint8_t rx, const uint32_t* adj = nullptr, uint32_t nadj = 0, uint8_t scale = 1);
-    // DENSE run for 2-3 rows at once (program.h): target t (COEFS word: lane opcodes `ops`, `rx`;
-    // rows i < hi of the run; ADJ additions adj[0..nadj)) accumulates into acc_t.  The op stays a
-    // shareable combine when it ends in op_store_shared stores only.
-    struct DenseCoefs { uint64_t ops; uint8_t rx; uint32_t hi; const uint32_t* adj; uint32_t nadj; };
-    void op_accr_dense_multi(uint32_t row0, uint32_t stride, uint32_t count, uint32_t len, uint32_t col0,
-                             const DenseCoefs* t, uint32_t nt);
+    // A Siamese row's direct dense range [0, hi) for up to three rows of nested ranges (t[0].hi <=
+    // t[1].hi <= ..., `runs` those of the longest), as both codecs emit it: the range is cut into
+    // chunks of `split` elements (0: one chunk); each chunk is one op of DENSE runs -- one ACCR +
+    // RANGE per run piece, one COEFS word per row that reaches into the chunk, its pair entries
+    // (DenseTarget::pairs, from draw_dense_pairs) written as ADJ words in place -- that ends in the
+    // rows' stores: a row over one chunk (parts == nullptr) is finished there, loose terms, footer
+    // and all; a row over several stores the chunk's partial sum into parts[c] and is summed by an
+    // op of its own one level up (parts, loose terms, footer) unless dst is kNoRow (the decoder's
+    // rows take the partial sums as terms).  With skip_empty a chunk that holds no packet of a run
+    // has no op (and no partial row).  Every word goes into instruction space reserved once, and
+    // each op's span, full length, cost class, level and byte counts come from the chunk's counts.
+    struct DenseTarget {
+        uint64_t ops;            // lane opcodes, 6 bits each
+        uint8_t rx;
+        uint32_t hi;             // end of the row's range
+        const uint32_t* pairs;   // rel << 8 | coef, ascending
+        uint32_t npairs;
+        RowId dst;
+        const RowId* parts;      // one per chunk of [0, hi)
+        uint32_t nparts;
+        const Term* loose;
+        uint32_t nloose;
+        const uint8_t* footer;
+        uint32_t flen;
+    };
+    void emit_dense_range(const DenseRun* runs, size_t nruns, const DenseTarget* t, uint32_t n, uint32_t split,
+                          uint32_t len, bool skip_empty);
     // STORE (+FOOTER) of acc_a at the end of an op whose row batches waves may split: the executor
     // reduces each stored accumulator across the waves (at most three stores, the op's last words).
     void op_store_shared(RowId dst, uint32_t len, uint32_t acc, const uint8_t* footer, uint32_t footer_len);
@@ -210,10 +264,12 @@ public:
     // opcodes `ops`, `rx`, coefficient additions adj[0..nadj) as op_accr_dense takes them): the
     // decoder's elimination of received originals straight from the packets.  combine() emits it
     // as one DENSE run scaled by the term's coefficient.
+    // (keys[0..nadj): pair entries rel << 8 | coef on the run's packets, rel0 the run's first)
     Term dense_run_term(uint32_t off0, uint32_t stride, uint32_t count, uint32_t col0, uint64_t ops, uint8_t rx,
-                        const uint32_t* adj, uint32_t nadj, uint32_t len) {
+                        const uint32_t* keys, uint32_t nadj, uint32_t rel0, uint32_t len) {
         const uint32_t at = (uint32_t)run_adj_.size();
-        run_adj_.insert(run_adj_.end(), adj, adj + nadj);
+        run_adj_.resize(at + nadj);
+        for (uint32_t i = 0; i < nadj; ++i) run_adj_[at + i] = ((keys[i] >> 8) - rel0) << 16 | (keys[i] & 0xffu) << 8;
         runs_.push_back(RunRef{TAMD_R_DENSE, rx, off0, stride, count, col0, ops, at, nadj});
         return Term{kRunFlag | (uint32_t)(runs_.size() - 1), len, 1};
     }
@@ -226,7 +282,9 @@ public:
     void op_storec_part(RowId dst, uint32_t units, uint32_t len, uint32_t cap, const uint8_t* c, bool first);
     // ACC of a part of row `src` (its level is the row's).
     void op_acc_part(RowId src, uint32_t units, uint8_t coef, uint32_t len, uint32_t acc);
-    uint32_t end_op(uint32_t min_level = 1);  // returns level; rows stored get that level
+    uint32_t end_op(uint32_t min_level = 1) {  // returns level; rows stored get that level
+        return close_op((uint32_t)instrs_.size(), min_level);
+    }
 
     bool empty() const { return ops_.empty(); }
     void clear();
@@ -280,6 +338,10 @@ private:
     std::vector<uint32_t> run_adj_;  // ADJ words of DENSE run terms
     size_t cur_written_begin_ = 0;
     uint64_t acc_bytes_ = 0, store_bytes_ = 0, cur_acc_begin_ = 0;
+    // cost class thresholds (end_op; TONK_AMD_CLASS, read when the builder is made)
+    uint64_t cls_div_ = 2, cls_t1_ = 64, cls_t2_ = 32, cls_t3_ = 12, cls_r0_ = 48;
+    // end_op for an op whose words end at instruction index `end` (a reservation may reach past it)
+    uint32_t close_op(uint32_t end, uint32_t min_level);
 };
 
 // ---------------------------------------------------------------------------------------------
