@@ -463,7 +463,7 @@ int oracle_recovery_row(const oracle_recovery_meta* m, oracle_get_row_fn get_row
    restated here (not included) so this file stays a stand-alone checker.
    ------------------------------------------------------------------------------------------ */
 enum { I_ACC = 1, I_STORE = 2, I_FOOTER = 3, I_CLEAR = 4, I_ACC3 = 5, I_STOREC = 6, I_ACCR = 7, I_RANGE = 8,
-       I_TARGETS = 9, I_COEFS = 10 };
+       I_TARGETS = 9, I_COEFS = 10, I_ADJ = 11 };
 enum { R_LANE3 = 1, R_CAUCHY = 2, R_CONST = 3, R_MULTI = 4, R_DENSE = 5 };
 
 /* Each op owns three accumulators of `span` bytes (program.h):
@@ -485,7 +485,10 @@ enum { R_LANE3 = 1, R_CAUCHY = 2, R_CONST = 3, R_MULTI = 4, R_DENSE = 5 };
            lane-sum combination of a Siamese row (SiameseEncoder.cpp:1046-1098) packet by packet;
            with p = 2 or 3 targets: p COEFS words (cap = ADJ words | hi << 16), each followed by its
            ADJ words, target t adding rows k < hi_t into acc_t (rows of nested sum ranges); one
-           target: w0 bits 24..31 = s > 1 scales every coefficient (decoder eliminations) */
+           target: w0 bits 24..31 = s > 1 scales every coefficient (decoder eliminations)
+           ADJ   w0 = 11 | four dwords d = idx << 16 | delta << 8 (dword 0 carries the kind): the words
+           after a COEFS word (COEFS.cap & 0xffff of them); row idx of the run takes coefficient ^
+           delta for that COEFS word's target (delta 0: an empty entry) */
 int oracle_run_program(uint8_t* arena, size_t arena_bytes,
                        const uint32_t* ops, unsigned n_ops,
                        const uint32_t* instrs, unsigned n_instrs)
@@ -537,6 +540,9 @@ int oracle_run_program(uint8_t* arena, size_t arena_bytes,
                     tg = w + 8;
                     if ((tg[0] & 0xff) != (mode == R_MULTI ? I_TARGETS : I_COEFS)) { free(acc); return -16; }
                     if (mode == R_DENSE && p < 2 && k + 2 + tg[3] >= count) { free(acc); return -18; }
+                    if (mode == R_DENSE && p < 2)
+                        for (uint32_t aw = 0; aw < tg[3]; ++aw)
+                            if ((tg[4 + 4 * aw] & 0xff) != I_ADJ) { free(acc); return -23; }
                 }
                 if (mode == R_DENSE && p >= 2) {
                     /* p targets: COEFS_t (cap = ADJ words | hi << 16) + its ADJ words each; target t
@@ -551,6 +557,9 @@ int oracle_run_program(uint8_t* arena, size_t arena_bytes,
                         at += 1 + (cw[t][3] & 0xffffu);
                     }
                     if (at > count) { free(acc); return -22; }
+                    for (uint32_t t = 0; t < p; ++t)
+                        for (uint32_t aw = 0; aw < (cw[t][3] & 0xffffu); ++aw)
+                            if ((cw[t][4 + 4 * aw] & 0xff) != I_ADJ) { free(acc); return -23; }
                     for (uint32_t e = 0; e < n; ++e) {
                         const size_t base = ((size_t)w[1] + (size_t)e * stride) * 64u;
                         const unsigned col = (unsigned)(((uint64_t)col0 + (uint64_t)e * cstep) % 0x400000u);

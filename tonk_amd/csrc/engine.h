@@ -213,7 +213,7 @@ public:
     // A strided run of level-0 rows (program.h ACCR); row0/stride in 64-B units.
     void op_accr(uint32_t mode, uint32_t param, uint32_t row0, uint32_t stride, uint32_t count, uint32_t len,
                  uint32_t col0, uint32_t cstep);
-    // MULTI run: targets t[a] = kind | p << 8 | hi << 16 accumulate into acc_a (program.h).
+    // MULTI run: targets t[a] = kind | p << 2 | lo << 10 | hi << 21 accumulate into acc_a (program.h).
     void op_accr_multi(uint32_t row0, uint32_t stride, uint32_t count, uint32_t len, uint32_t col0, uint32_t cstep,
                        const uint32_t t[3]);
     // DENSE run: a Siamese row's dense part over a run of level-0 packets (program.h); `ops` holds

@@ -45,6 +45,48 @@
 // GF(2^8) arithmetic, so an op is split into byte slices that the device runs in parallel with
 // no synchronisation.  Ops in one launch never read a row another op of the same launch writes
 // (the host orders dependent ops into later launches: "levels").
+//
+// Preconditions.  The executor checks nothing: a program that breaks one of these rules reads or
+// writes outside its rows, or computes something else than the interpreter (the one case where the
+// two are known to part is named).  Every emitter keeps them; tests/native/exec_check.cpp
+// (validate_program) restates them and refuses to launch a program that fails one.
+//   - An op's span is a multiple of 8 and covers every length and every store's cap it uses;
+//     full <= every length it uses (ProgramBuilder::close_op computes both).
+//   - ACC / ACC3: len >= 1; the accumulator of ACC and STORE is 0, 1 or 2.
+//   - STORE: a FOOTER word follows; footer length <= 8; len + footer length <= cap.  STORE and
+//     STOREC: len <= cap, and cap is a multiple of 8 (the executor stores whole 8-byte words below
+//     cap; the emitters pass a row's capacity or a whole number of units).
+//   - ACCR: a RANGE word follows; count >= 1 and len >= 1; col0 < 2^22.
+//   - A LANE3 run does not cross the 22-bit column wrap: col0 + (count - 1) * cstep < 2^22 (the
+//     executor steps the column value index from col0 without reducing the column; LaneSums
+//     never merges packets across the wrap into one run, engine.h).  CAUCHY, CONST, MULTI and
+//     DENSE runs may cross it (the column enters mod 64, or is reduced mod 2^22).
+//   - CAUCHY (a run's p, a MULTI target's p): p < 192 (SiameseCommon.h kCauchyMaxRows; the
+//     executor's table of inverses holds x = p + 64 up to 255).
+//   - MULTI: a TARGETS word follows; a target is unused (the whole word 0), CAUCHY or CONST (p of a
+//     CONST target is ignored: the coefficient is 1); lo <= hi <= count, both 11-bit, so a run
+//     that a window ends holds at most 2047 rows.  (With lo > hi the interpreter takes no row, the
+//     executor every row from lo on.)
+//   - DENSE: p = 0 (one target: one COEFS word, cap = its ADJ words, w0 bits 24..31 its scale) or
+//     p = 2, 3 (that many COEFS words, each cap = ADJ words | hi << 16 and followed by its ADJ
+//     words; no scale).  The ranges are nested: hi_0 <= hi_1 <= hi_2 <= count.
+//   - ADJ entries of one COEFS word are ascending by row index (equal indices may repeat), empty
+//     entries (delta 0, the whole dword 0) only at the end of the last word: the executor walks
+//     them once with a cursor, 64 rows at a time.  (The interpreter scans them all per row.)
+//     An entry's index is 16 bits: it can name the first 65536 rows of a run.
+//   - Every byte an instruction touches lies inside one allocated row: [row, row + len) of ACC,
+//     ACC3 and of each row of a run (row0 + k * stride, k < count), [row, row + cap) of a store.
+//     Rows are whole 64-byte units, the executor's loads are 8 or 16 bytes at offsets below len
+//     (lanes past len re-read the row's start) and a run's loads past its end re-read its last
+//     row, so these rules keep every load of the executor inside the row as well.
+//   - No op reads a row that an op of the same level writes -- itself included: the loads of an
+//     instruction batch are issued before the batch's stores -- and no two ops of a level write
+//     the same row.  A row may be written again at a later level.
+//   - An op flagged pure (ProgramBuilder::op_pure) holds only ACC into acc_0, CONST / CAUCHY /
+//     DENSE runs and, as its last words, one STORE + FOOTER (1) or up to three, one per
+//     accumulator of its multi-target DENSE runs (2): waves that share the op skip those stores
+//     and the reduction finds them from the op's end.  Server::build declines a program with a
+//     multi-target DENSE run (tamd_serve has no code for it).
 #pragma once
 #include <stdint.h>
 
