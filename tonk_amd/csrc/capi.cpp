@@ -242,8 +242,6 @@ void report_disable(const char* where) {
 }
 #define DISABLE(codec) (report_disable(__func__), (codec)->set_disabled())
 
-bool capi_combine();
-
 // Packets added to a codec wait in the codec's own pinned staging (two halves) and reach the
 // arena in one H2D copy + one scatter launch: before the codec's next program, or when a half
 // fills up.  Adds never take the device lock.
@@ -398,12 +396,9 @@ struct Codec {
         // than 16 terms are read as rows -- inlining both grows a program quadratically with L
         // (a burst of losses under Tonk made single programs of 8 MB, and the slot growth that
         // follows stalls every codec).
-        static const uint32_t bs = getenv("TONK_AMD_CAPI_BACKSUB") ? (uint32_t)atoi(getenv("TONK_AMD_CAPI_BACKSUB")) : 2u;
-        static const uint32_t ex = getenv("TONK_AMD_CAPI_EXPAND") ? (uint32_t)atoi(getenv("TONK_AMD_CAPI_EXPAND")) : 16u;
-        ctx.backsub_rows = bs ? bs : ~0u;  // (0: never materialize / always inline)
-        ctx.ex.expand_limit = ex ? ex : ~0u;
-        static const bool short_scans = !getenv("TONK_AMD_CAPI_SHORT_SCANS") || atoi(getenv("TONK_AMD_CAPI_SHORT_SCANS")) != 0;
-        ctx.short_scans = short_scans;  // (A/B: 0 restores the chain level)
+        ctx.backsub_rows = 2;
+        ctx.ex.expand_limit = 16;
+        ctx.short_scans = true;
         static std::atomic<unsigned> next{0};
         staging.stream = next.fetch_add(1) % g_rt->dev.stream_count();
         staging.bar = (g_bar & 1u) != 0;
@@ -491,7 +486,7 @@ struct CDecoder : Codec {
     std::vector<SiameseOriginalPacket> out;
 };
 
-// Combined launches (TONK_AMD_CAPI_COMBINE=0 turns them off).  Codecs of different connections
+// Combined launches.  Codecs of different connections
 // call siamese_encode / siamese_decode concurrently, and each call needs its program run and read
 // back before it returns (siamese.cpp:158-167; TonkineseOutgoing.cpp:1284-1328 sends the result
 // at once).  A caller whose program is ready queues it; the first caller to find no leader
@@ -502,10 +497,6 @@ struct CDecoder : Codec {
 // then waits for its own event without a lock.  There is one such queue per launch stream and a
 // codec keeps its stream, so its staged uploads, programs and reads stay in order while the
 // streams' batches overlap on the device.
-bool capi_combine() {
-    static const bool on = !(getenv("TONK_AMD_CAPI_COMBINE") && atoi(getenv("TONK_AMD_CAPI_COMBINE")) == 0);
-    return on;
-}
 // The event behind a combined batch, released by the last of its callers to finish waiting.
 struct BatchDone {
     void* ev = nullptr;
@@ -657,52 +648,33 @@ bool run_and_read(Codec& c, const std::vector<Device::HostCopy>& reads) {
         }
         c.used_launch = true;
     }
-    void* ev = nullptr;
-    BatchDone* batch = nullptr;
-    bool ok = true;
-    if (capi_combine()) {
-        RunReq req;
-        req.c = &c;
-        req.reads = &reads;
-        {
-            const unsigned st = c.staging.stream;
-            RunQueue& rq = g_run[st];
-            std::unique_lock<std::mutex> lk(rq.mu);
-            rq.q.push_back(&req);
-            req.cv.wait(lk, [&req, &rq] { return req.launched || !rq.leader; });
-            if (!req.launched) {
-                rq.leader = true;
-                std::vector<RunReq*> b;
-                while (!req.launched) {
-                    lk.unlock();
-                    launch_batch(b, st);  // (takes the queue under the device lock)
-                    lk.lock();
-                    for (RunReq* r : b) {
-                        r->launched = true;
-                        if (r != &req) r->cv.notify_one();
-                    }
+    RunReq req;
+    req.c = &c;
+    req.reads = &reads;
+    {
+        const unsigned st = c.staging.stream;
+        RunQueue& rq = g_run[st];
+        std::unique_lock<std::mutex> lk(rq.mu);
+        rq.q.push_back(&req);
+        req.cv.wait(lk, [&req, &rq] { return req.launched || !rq.leader; });
+        if (!req.launched) {
+            rq.leader = true;
+            std::vector<RunReq*> b;
+            while (!req.launched) {
+                lk.unlock();
+                launch_batch(b, st);  // (takes the queue under the device lock)
+                lk.lock();
+                for (RunReq* r : b) {
+                    r->launched = true;
+                    if (r != &req) r->cv.notify_one();
                 }
-                rq.leader = false;
-                if (!rq.q.empty()) rq.q.front()->cv.notify_one();  // the next caller queued leads
             }
+            rq.leader = false;
+            if (!rq.q.empty()) rq.q.front()->cv.notify_one();  // the next caller queued leads
         }
-        ok = req.ok;
-        batch = req.done;
-    } else {
-        DevLock dl;
-        Device& dev = g_rt->dev;
-        dev.select_stream(c.staging.stream);
-        const uint64_t launches = dev.stats().launches;
-        c.staging.send_locked(dev);  // packets added since the last program land first
-        if (!ctx.pb.empty()) {
-            dev.run(&ctx);
-            g_programs.fetch_add(1, std::memory_order_relaxed);
-            g_launches.fetch_add(dev.stats().launches - launches, std::memory_order_relaxed);
-        }
-        for (const Device::HostCopy& x : reads) dev.download_pinned(x.host, x.arena_off, x.len);
-        ev = dev.record_event();
-        ok = !dev.failed();
     }
+    bool ok = req.ok;
+    BatchDone* batch = req.done;  // (set by the launch_batch that launched this request)
     if (g_watch) {
         g_prepare_ns.fetch_add((uint64_t)(t1 - t0), std::memory_order_relaxed);
         g_run_ns.fetch_add((uint64_t)(now_ns() - t1), std::memory_order_relaxed);
@@ -711,19 +683,19 @@ bool run_and_read(Codec& c, const std::vector<Device::HostCopy>& reads) {
     ctx.finish_flush();
     const int64_t w0 = now_ns();
     if (g_in_wait.fetch_add(1) == 0) g_in_wait_since.store(w0);
-    ok = Device::event_wait(batch ? batch->ev : ev) && ok;
+    ok = Device::event_wait(batch->ev) && ok;
     if (g_in_wait.fetch_sub(1) == 1) g_in_wait_since.store(0);
     g_waits.fetch_add(1, std::memory_order_relaxed);
     g_wait_ns.fetch_add((uint64_t)(now_ns() - w0), std::memory_order_relaxed);
-    if (!batch || batch->left.fetch_sub(1) == 1) {
+    if (batch->left.fetch_sub(1) == 1) {
         DevLock dl;
-        g_rt->dev.event_release(batch ? batch->ev : ev);
+        g_rt->dev.event_release(batch->ev);
         ok = ok && !g_rt->dev.failed();
         delete batch;
     } else {
         ok = ok && !g_rt->dev.failed();
     }
-    c.staging.all_settled();         // every staged copy was enqueued before `ev`
+    c.staging.all_settled();         // every staged copy was enqueued before the batch's event
     ctx.rows.release_up_to(done);  // every program of this codec up to `done` has completed
     return ok;
 }

@@ -30,14 +30,11 @@ extern "C" __global__ void tamd_copy_in(const uint4*, uint4*, uint32_t, const ui
 namespace {
 // Program uploads below this many bytes go through tamd_copy_in (a launch whose threads read the
 // pinned bytes) instead of the DMA engine, on devices that asked for it (set_small_uploads: few
-// streams, the C ABI); TONK_AMD_SMALL_UPLOAD overrides the size (0: never, A/B).
-size_t small_upload() {
-    static const size_t v = getenv("TONK_AMD_SMALL_UPLOAD") ? (size_t)atoll(getenv("TONK_AMD_SMALL_UPLOAD")) : (256u << 10);
-    return v;
-}
+// streams, the C ABI).
+constexpr size_t kSmallUpload = 256u << 10;
 // Two host -> device ranges, by the copy kernel when small, else by DMA.
 void upload2(bool small_ok, void* d0, const void* h0, size_t b0, void* d1, const void* h1, size_t b1, hipStream_t st) {
-    if (small_ok && b0 + b1 < small_upload()) {
+    if (small_ok && b0 + b1 < kSmallUpload) {
         const uint32_t n0 = (uint32_t)((b0 + 15) / 16), n1 = (uint32_t)((b1 + 15) / 16);
         const uint32_t blocks = std::min<uint32_t>(256u, (n0 + n1 + 255) / 256);
         if (n0 + n1)
@@ -49,7 +46,6 @@ void upload2(bool small_ok, void* d0, const void* h0, size_t b0, void* d1, const
     if (b1) hipMemcpyAsync(d1, h1, b1, hipMemcpyHostToDevice, st);
 }
 }  // namespace
-size_t tamd::Device::small_upload_limit() { return small_upload(); }
 
 struct GenDescDev { uint32_t row, index, len, pad; unsigned long long seed; };
 struct DigestDescDev { uint32_t row, skip, len, pad; };
@@ -271,8 +267,6 @@ bool Device::init(int device, uint64_t arena_bytes) {
         HIPCHK(hipMalloc((void**)&arena_, arena_bytes_));
     }
     HIPCHK(hipMemsetAsync(arena_, 0, arena_bytes_, s));
-    if (getenv("TONK_AMD_DEBUG_ALLOC"))  // (diagnostics: placement of the arena)
-        fprintf(stderr, "tonk_amd: arena %p, %llu bytes\n", (void*)arena_, (unsigned long long)arena_bytes_);
     if (!gf_init()) { error_ = "gf self test failed"; return false; }
     // kernels.hip TAMD_GF_DWORDS: perm tables, inv[256], sqr[256], then the lane table: for
     // i = 0..252 (column value cx = 3 + i) the perm dwords of cx and of cx^2, then the Cauchy table
@@ -620,8 +614,7 @@ uint64_t Device::close_program(int h, Part* const* parts, size_t n) {
     // has XCD affinity i mod 8: its items go to positions p with p mod 8 == i mod 8 as far as the
     // counts allow, and the executor runs position p of a class block on a workgroup of XCD p mod 8
     // (exec_level), so one stream's ops -- which read the same packets -- share that XCD's L2.
-    // (TONK_AMD_XCD_AFFINITY=0: parts in order, A/B.)
-    static const bool affinity = !getenv("TONK_AMD_XCD_AFFINITY") || atoi(getenv("TONK_AMD_XCD_AFFINITY")) != 0;
+    // A single part's items are copied in order.
     uint64_t* items = (uint64_t*)slot.host;
     size_t at = 0;
     for (uint32_t b = 0; b < B && !failed_; ++b) {
@@ -638,7 +631,7 @@ uint64_t Device::close_program(int h, Part* const* parts, size_t n) {
             failed_ = true;
             break;
         }
-        if (!affinity || n < 2) {
+        if (n < 2) {
             for (size_t i = 0; i < n; ++i) {
                 const Part& p = *parts[i];
                 if (b + 1 >= p.bucket_start.size()) continue;
@@ -884,15 +877,15 @@ void Device::fill(size_t c) {
 void Device::launch_step(Inflight* fresh, unsigned long long* stamps) {
     tamd_segments sg;
     memset(&sg, 0, sizeof(sg));
-    uint32_t cnt = 0, coop = 0;
-    uint32_t seg_level[TAMD_MAX_SEGMENTS], seg_coop[TAMD_MAX_SEGMENTS];
+    uint32_t cnt = 0, coop = 0;  // coop: the first segment's class-0 items that may be shared
+    uint32_t seg_level[TAMD_MAX_SEGMENTS];
     auto add = [&](Inflight& p) {
         if (p.done()) return;
         const uint32_t l = p.next++;
         const uint32_t c = p.level_items[l];
         if (!c) return;
         seg_level[sg.n] = l;
-        seg_coop[sg.n] = p.level_coop[l];
+        if (!sg.n) coop = p.level_coop[l];
         tamd_segment& g = sg.s[sg.n++];
         g.ops = p.ops;
         g.instrs = p.instrs;
@@ -904,41 +897,17 @@ void Device::launch_step(Inflight* fresh, unsigned long long* stamps) {
     for (Inflight& p : progs_) add(p);
     if (fresh) add(*fresh);
     if (!cnt) return;
-    // Segment order = the order waves claim items in (A/B, TONK_AMD_SEG_ORDER): 0 programs
-    // oldest first (deepest level first, the new program's level 1 last); 1 level 2, level 1,
-    // then the rest; 2 level 1, level 2, then the rest; 3 the rest, then level 1, then level 2.
-    static const int seg_order = getenv("TONK_AMD_SEG_ORDER") ? atoi(getenv("TONK_AMD_SEG_ORDER")) : 0;
-    if (seg_order && sg.n > 1) {
-        static const uint32_t rank_of[4][3] = {{0, 0, 0}, {1, 0, 2}, {0, 1, 2}, {1, 2, 0}};  // [order][L1, L2, rest]
-        tamd_segment tmp[TAMD_MAX_SEGMENTS];
-        uint32_t tl[TAMD_MAX_SEGMENTS], tc[TAMD_MAX_SEGMENTS], m = 0;
-        for (uint32_t pass = 0; pass < 3; ++pass)
-            for (uint32_t k = 0; k < sg.n; ++k) {
-                const uint32_t cls = seg_level[k] == 1 ? 0u : seg_level[k] == 2 ? 1u : 2u;
-                if (rank_of[seg_order & 3][cls] != pass) continue;
-                tmp[m] = sg.s[k];
-                tl[m] = seg_level[k];
-                tc[m] = seg_coop[k];
-                ++m;
-            }
-        for (uint32_t k = 0; k < sg.n; ++k) {
-            sg.s[k] = tmp[k];
-            seg_level[k] = tl[k];
-            seg_coop[k] = tc[k];
-        }
-    }
-    coop = seg_coop[0];
+    // Segment order = the order waves claim items in: programs oldest first (deepest level
+    // first, the new program's level 1 last).
     // Items class by class across the segments: the launch's long items (every level's class 0)
-    // are taken first (TONK_AMD_CLASS_MAJOR=0: segment by segment, A/B)
-    static const bool class_major = !getenv("TONK_AMD_CLASS_MAJOR") || atoi(getenv("TONK_AMD_CLASS_MAJOR")) != 0;
-    sg.flags = class_major ? 1u : 0u;
+    // are taken first (program.h: the host never sends flags = 0)
+    sg.flags = 1u;
     hipStream_t st = (hipStream_t)stream_;
     // Class-0 ops are shared by a workgroup only in launches too small to fill the chip twice
     // over with single-wave items; in the big ones they run as ordinary (first) items.  Only the
     // first segment's class-0 items (they lead it) can be shared.  A shared item gets a
     // workgroup of its own, the single-wave items four to a workgroup beside them.
-    static const int share_mode = getenv("TONK_AMD_SHARE") ? atoi(getenv("TONK_AMD_SHARE")) : 0;  // A/B (profiling)
-    const uint32_t shared = (share_mode == 1 || (share_mode == 0 && cnt < 2u * 4u * max_grid_)) ? coop : 0u;
+    const uint32_t shared = cnt < 2u * 4u * max_grid_ ? coop : 0u;
     uint32_t grid = shared + (cnt - shared + 3) / 4;
     if (grid > max_grid_) grid = max_grid_;
     hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -1036,9 +1005,6 @@ uint64_t Device::launch() {
     HIPCHK(hipGetLastError());
     const double up_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count();
     stats_.upload_enqueue_ms += up_ms;
-    if (up_ms > 1.0 && getenv("TONK_AMD_TRACE_UPLOADS"))
-        fprintf(stderr, "tonk_amd: program %llu: H2D enqueue of %zu bytes took %.3f ms\n",
-                (unsigned long long)(ticket_ + 1), P.total, up_ms);
     if (up_ms > stats_.upload_enqueue_max_ms) stats_.upload_enqueue_max_ms = up_ms;
     Inflight cur;
     cur.instrs = slot.dev_off;

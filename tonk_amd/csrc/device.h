@@ -95,7 +95,6 @@ public:
     // Enqueue the pending programs of `ctxs` as one merged program (asynchronous).  Returns the
     // completion ticket (monotonic); call completed() / wait() with it.
     uint64_t run(Context* const* ctxs, size_t n);
-    uint64_t run(Context* ctx) { return run(&ctx, 1); }
     // The same in three phases so host threads can fill their part of the merged program in
     // parallel: begin() lays the program out (ops grouped by level, then by context) and waits
     // for the staging slot; fill(i) copies context i (thread safe for distinct i); launch()
@@ -132,8 +131,7 @@ public:
     void set_assembly_slots(size_t count, size_t host_mb);
     // Small programs (few-stream sessions, the C ABI) are uploaded by a copy kernel instead of DMA
     // (its latency, not its rate, is what a single program waits for); call before init.
-    void set_small_uploads(bool on) { small_uploads_ = on && small_upload_limit() > 0; }
-    static size_t small_upload_limit();
+    void set_small_uploads(bool on) { small_uploads_ = on; }
     // Whether a program of `recs` records (instructions + ops) and `items` work items fits a slot;
     // ensure_assembly grows every slot to fit (drains the device first: no program may be open).
     bool assembly_fits(size_t recs, size_t items) const;

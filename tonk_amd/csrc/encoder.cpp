@@ -697,11 +697,9 @@ Result Encoder::generate_cauchy(RecoveryOut& out) {
     // The row's op is emitted with the group (at the latest by pre_flush, so within this
     // program); its readers must already see the level it will be written at.
     ctx_->rows.set_level(out.row, 1);
-    static const uint32_t max_group = getenv("TONK_AMD_NO_MULTI") ? 1u : 3u;
-    // (A/B knob; at most 2047: the run indices of a TARGETS word are 11-bit)
-    static const uint32_t span = getenv("TONK_AMD_MULTI_SPAN")
-                                     ? std::min<uint32_t>(2047u, std::max(1, atoi(getenv("TONK_AMD_MULTI_SPAN"))))
-                                     : kGroupSpan;
+    const uint32_t max_group = 3;  // (grp_)
+    // (at most 2047: the run indices of a TARGETS word are 11-bit)
+    const uint32_t span = kGroupSpan;
     const uint32_t end_col = to_column(count_);
     // A row over a long window stays a pure combine of its own (the executor shares those across
     // a workgroup); a group is one wave's chain, and a long one would set the launch's tail.
@@ -805,11 +803,10 @@ void Encoder::add_dense(uint32_t row, uint32_t recovery_bytes, Sym& rec) {
 // Rows are queued (dgrp_) and emitted by emit_dense_group: rows of one sum range share its
 // packets, so up to three of them are one op per chunk, each packet loaded once for all.
 bool Encoder::defer_dense(uint32_t row, uint32_t recovery_bytes, const RecoveryOut& out) {
-    static const uint32_t max_group = getenv("TONK_AMD_NO_DENSE_GROUP") ? 1u : 3u;  // (A/B knob)
+    const uint32_t max_group = 3;  // (dgrp_)
     // A group's op is one work item per slice (one wave, or one workgroup in small launches), so
     // its products per item are bounded as a lone row's are: packets per chunk x targets
-    static const uint32_t max_work = getenv("TONK_AMD_DENSE_WORK") ? (uint32_t)atoi(getenv("TONK_AMD_DENSE_WORK"))
-                                                                  : kDenseGroupWork;
+    const uint32_t max_work = kDenseGroupWork;
     const uint32_t lo = sum_abs_start(), hi = base_ + count_;
     const uint32_t split = ctx_->dense_split;
     const uint32_t rows = split && hi - lo > split ? split : hi - lo;
@@ -914,15 +911,11 @@ void Encoder::add_light(uint32_t row, Sym& rec) {
 // Short sum ranges (the usual case with acknowledgements: each Siamese row follows a sum reset)
 // are read straight from the packets; long ones through the running lane sums.
 bool Encoder::direct_sums() const {
-    static const uint32_t direct_max = getenv("TONK_AMD_DIRECT") ? (uint32_t)atoi(getenv("TONK_AMD_DIRECT"))
-                                                                  : kDirectMax;
-    static const int direct_mode = getenv("TONK_AMD_DIRECT_MODE") ? atoi(getenv("TONK_AMD_DIRECT_MODE")) : 0;
     const uint32_t range = count_ + sum_erased_ - sum_start_;
-    const bool fresh = sum_end_ == sum_start_;
     // Direct reads pay per run (a DENSE run's coefficient setup and first row loads); packets
     // added one by one with host copies (the C ABI) are runs of one, where the lane sums' batched
     // single-row reads are far cheaper: direct only while the range's runs average kDirectMinRun.
-    bool direct = range <= direct_max && (direct_mode == 0 || fresh || (direct_mode == 2 && range <= 128));
+    bool direct = range <= kDirectMax;
     if (direct && range) direct = (segs_.size() - seg_index_at(sum_abs_start())) * kDirectMinRun <= range;
     return direct;
 }

@@ -85,7 +85,7 @@ public:
     static const uint32_t kDenseSplit = 48;
     // Siamese rows whose sum range is at most this many packets read it straight from the packets
     // (defer_dense, and the decoder's Decoder::eliminate_direct); longer ones through the running
-    // lane sums (TONK_AMD_DIRECT overrides the encoder's).
+    // lane sums.
     static const uint32_t kDirectMax = 512;
     static const uint32_t kDirectMinRun = 8;  // packets per run the direct reads need on average
     Encoder(Context* ctx, uint32_t row_bytes, HostRelease release = nullptr, void* user = nullptr);
@@ -309,7 +309,7 @@ private:
         Sym loose;                   // the others, as rows
         std::vector<RowId> parts;    // partial sums, one per chunk (ranges over one chunk: none)
     };
-    // Packets x rows one group op may take per chunk (TONK_AMD_DENSE_WORK overrides): a chunk
+    // Packets x rows one group op may take per chunk: a chunk
     // of 192 packets (kDenseSplit) is one row's work; its items are the level's longest.
     static const uint32_t kDenseGroupWork = 144;
     DenseTarget dgrp_[3];

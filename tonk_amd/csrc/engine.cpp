@@ -133,18 +133,7 @@ void RowTable::release_up_to(uint64_t completed) {
 // ---------------------------------------------------------------------------------------------
 static void push_store(InstrVec& v, uint32_t off, uint32_t len, uint32_t cap,
                        const uint8_t* footer, uint32_t flen, uint32_t acc = 0);
-ProgramBuilder::ProgramBuilder(RowTable* rows) : rows_(rows) {
-    // (TONK_AMD_CLASS="rows_div,t1,t2,t3,rows0": A/B knob for the cost class thresholds of end_op)
-    if (const char* e = getenv("TONK_AMD_CLASS")) {
-        unsigned long long v[5] = {cls_div_, cls_t1_, cls_t2_, cls_t3_, cls_r0_};
-        sscanf(e, "%llu,%llu,%llu,%llu,%llu", &v[0], &v[1], &v[2], &v[3], &v[4]);
-        cls_div_ = v[0] ? v[0] : 2;
-        cls_t1_ = v[1];
-        cls_t2_ = v[2];
-        cls_t3_ = v[3];
-        cls_r0_ = v[4];
-    }
-}
+ProgramBuilder::ProgramBuilder(RowTable* rows) : rows_(rows) {}
 
 // (the vectors keep the capacity the previous programs reached: pushes do not allocate)
 void ProgramBuilder::clear() {
@@ -612,9 +601,9 @@ uint32_t ProgramBuilder::close_op(uint32_t end, uint32_t min_level) {
     // Cost class from the op's length in the executor's terms: instructions, and row loads
     // (an ACCR run is `count` rows); class 0 is the most expensive and starts first.
     const uint64_t rows = (acc_bytes_ - cur_acc_begin_) / 1024u;
-    const uint64_t cost = op.count + 4u * cur_runs_ + rows / cls_div_;
-    const uint32_t cls = (cur_pure_ && rows >= cls_r0_) ? 0u
-                         : cost >= cls_t1_ ? 1u : cost >= cls_t2_ ? 2u : cost >= cls_t3_ ? 3u : 4u;
+    const uint64_t cost = op.count + 4u * cur_runs_ + rows / kClsRowsDiv;
+    const uint32_t cls = (cur_pure_ && rows >= kClsRows0) ? 0u
+                         : cost >= kClsT1 ? 1u : cost >= kClsT2 ? 2u : cost >= kClsT3 ? 3u : 4u;
     const uint32_t bucket = TAMD_COST_CLASSES * level + cls;
     levels_.push_back(bucket);
     pure_.push_back(cur_pure_ ? (cur_multi_ ? 2 : 1) : 0);
@@ -788,11 +777,6 @@ void ExpansionTable::append(const RowTable& rows, RowId r, uint32_t len, uint8_t
 // ---------------------------------------------------------------------------------------------
 // LaneSums
 // ---------------------------------------------------------------------------------------------
-uint32_t LaneSums::chunk() {
-    static const uint32_t c = getenv("TONK_AMD_CHUNK") ? (uint32_t)atoi(getenv("TONK_AMD_CHUNK")) : 64u;  // A/B
-    return c ? c : 64u;
-}
-
 void LaneSums::reset(RowTable& rows) {
     if (!snaps_.empty()) {
         // Closed entries are reused across flushes: the swap hands this scan's lists to the entry
@@ -817,11 +801,6 @@ void LaneSums::reset(RowTable& rows) {
 
 static inline bool same_coefs(const uint8_t* a, const uint8_t* b) {
     return a[0] == b[0] && a[1] == b[1] && a[2] == b[2];
-}
-
-uint32_t LaneSums::dyn_fold_above() {
-    static const uint32_t v = getenv("TONK_AMD_DYN_FOLD") ? (uint32_t)atoi(getenv("TONK_AMD_DYN_FOLD")) : 2u;
-    return v;
 }
 
 // The dyn_ packets (and an earlier fold) into three rows, one combine each: every later read
@@ -875,7 +854,7 @@ void LaneSums::read(RowTable& rows, const ExpansionTable& ex, Sym& out, const ui
             snap = rows.alloc(content_);
             if (snap == kNoRow) return;  // caller checks arena exhaustion via RowTable
             // written by the scan's chain (or only) op
-            const uint32_t level = short_scan && at <= chunk() ? snap_level(rows, base_, 1) : snap_level(rows, base_);
+            const uint32_t level = short_scan && at <= kChunk ? snap_level(rows, base_, 1) : snap_level(rows, base_);
             rows.set_level(snap, level);
             snaps_.push_back(Snap{snap, at, {c[0], c[1], c[2]}, (uint8_t)level});
         }
@@ -885,11 +864,10 @@ void LaneSums::read(RowTable& rows, const ExpansionTable& ex, Sym& out, const ui
             if (base_[s] != kNoRow && c[s]) out.push_back(Term{base_[s], clip, c[s]});
     }
     TAMD_PROF_SCOPE(kLaneDyn);
-    const uint32_t fold_at = dyn_fold_above();
     // (only where expansions are limited -- the few-stream sessions and the C ABI, whose
     // decoders pile up recovered packets at high loss; the batched sessions inline everything
     // and a fold there costs a level for little: 1.05x the control time on the headline)
-    if (pb && fold_at && dyn_.size() >= fold_at && ex.expand_limit != ~0u) fold_dyn(rows, *pb, ex);
+    if (pb && dyn_.size() >= kDynFoldAbove && ex.expand_limit != ~0u) fold_dyn(rows, *pb, ex);
     for (unsigned s = 0; s < 3; ++s)
         if (fold_[s] != kNoRow && c[s]) out.push_back(Term{fold_[s], fold_len_ < limit ? fold_len_ : limit, c[s]});
     for (const T& d : dyn_) {
@@ -937,11 +915,6 @@ static void skip_packets(const std::vector<LaneSums::T>& terms, size_t& ri, uint
     }
 }
 
-uint32_t LaneSums::inline_max() {
-    static const uint32_t v = getenv("TONK_AMD_INLINE_SEG") ? (uint32_t)atoi(getenv("TONK_AMD_INLINE_SEG")) : 3u;  // A/B
-    return v;
-}
-
 // One scan = the lane's packets in order with snapshots (STOREC) at their read points.  A long
 // scan would be one wave walking hundreds of rows, so it is cut into chunks of at most kChunk
 // packets, split at every snapshot point: each chunk op (level 1) writes its three partial sums
@@ -962,7 +935,6 @@ void LaneSums::emit_scan(RowTable& rows, ProgramBuilder& pb, const RowId* base, 
             ++si;
         }
     };
-    const uint32_t kChunk = chunk();
     // (a snapshot promised a lower level than the chain's -- LaneSums::read -- keeps the scan one op)
     const uint32_t chain_level = snap_level(rows, base);
     uint32_t level = chain_level;
@@ -989,7 +961,7 @@ void LaneSums::emit_scan(RowTable& rows, ProgramBuilder& pb, const RowId* base, 
     }
 
     // Segments: cut at every snapshot point, and at most kChunk packets apart.  A segment of
-    // more than inline_max() packets is a chunk op (level 1) whose three partial sums go to one
+    // more than kInlineMax packets is a chunk op (level 1) whose three partial sums go to one
     // row of three parts; the chain op adds them.  A shorter one is walked by the chain op
     // itself: its packets are read once, where a chunk would write three partial rows and the
     // chain read them back (dense snapshots -- a recovery row every few lane packets -- made most
@@ -999,7 +971,6 @@ void LaneSums::emit_scan(RowTable& rows, ProgramBuilder& pb, const RowId* base, 
     segs.clear();
     const uint32_t wunits = (width + TAMD_ROW_UNIT - 1) / TAMD_ROW_UNIT;
     const uint32_t wcap = wunits * TAMD_ROW_UNIT;
-    const uint32_t imax = inline_max();
     uint32_t pos = 0;
     size_t sj = 0;
     while (pos < n) {
@@ -1008,7 +979,7 @@ void LaneSums::emit_scan(RowTable& rows, ProgramBuilder& pb, const RowId* base, 
         if (sj < snaps.size() && snaps[sj].after < end) end = snaps[sj].after;
         if (end > n) end = n;
         Seg g{pos, end - pos, kNoRow};
-        if (g.count <= imax) {
+        if (g.count <= kInlineMax) {
             skip_packets(terms, ri, rdone, g.count);
         } else {
             pb.begin_op();
@@ -1028,7 +999,7 @@ void LaneSums::emit_scan(RowTable& rows, ProgramBuilder& pb, const RowId* base, 
         if (base[s] != kNoRow) pb.op_acc(base[s], 1, rows.cap_bytes(base[s]), s);
     for (const Seg& g : segs) {
         snapshots(g.pos);
-        if (g.count <= imax) {
+        if (g.count <= kInlineMax) {
             emit_packets(pb, terms, ri, rdone, g.count);
         } else {
             skip_packets(terms, ri, rdone, g.count);

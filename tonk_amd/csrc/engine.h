@@ -338,8 +338,9 @@ private:
     std::vector<uint32_t> run_adj_;  // ADJ words of DENSE run terms
     size_t cur_written_begin_ = 0;
     uint64_t acc_bytes_ = 0, store_bytes_ = 0, cur_acc_begin_ = 0;
-    // cost class thresholds (end_op; TONK_AMD_CLASS, read when the builder is made)
-    uint64_t cls_div_ = 2, cls_t1_ = 64, cls_t2_ = 32, cls_t3_ = 12, cls_r0_ = 48;
+    // cost class thresholds (end_op): cost = instructions + 4 * runs + rows / kClsRowsDiv; class 1,
+    // 2, 3 from these costs up; class 0 is a pure op of at least kClsRows0 rows
+    static constexpr uint64_t kClsRowsDiv = 2, kClsT1 = 64, kClsT2 = 32, kClsT3 = 12, kClsRows0 = 48;
     // end_op for an op whose words end at instruction index `end` (a reservation may reach past it)
     uint32_t close_op(uint32_t end, uint32_t min_level);
 };
@@ -469,7 +470,7 @@ public:
     }
     // Append c[0]*sum_0 + c[1]*sum_1 + c[2]*sum_2 (current values, clipped to `limit` bytes).
     // With `pb`, packets produced in this program that have piled up (dyn_, each read as its
-    // expansion by every read) are first folded into three rows (dyn_fold_above()).
+    // expansion by every read) are first folded into three rows (kDynFoldAbove).
     // With `short_scan` (Context::short_scans), a snapshot taken while the scan is still one
     // op's length is promised the scan op's own level (1 over level-0 bases) instead of the chain
     // level, and the scan is then emitted as that one op.
@@ -486,10 +487,9 @@ private:
 public:
     // a run of `count` lane packets: rows off + k*stride, columns col + 8k (count 1: a single row)
     struct T { RowId row; uint32_t len, off, stride, count, col; };
-    static uint32_t chunk();  // longest packet walk of one scan op (see emit_scan)
-    // read() folds dyn_ once it holds this many packets (TONK_AMD_DYN_FOLD; 0: never)
-    static uint32_t dyn_fold_above();
-    static uint32_t inline_max();  // segments this short are walked by the chain op (emit_scan)
+    static constexpr uint32_t kChunk = 64;        // longest packet walk of one scan op (see emit_scan)
+    static constexpr uint32_t kDynFoldAbove = 2;  // read() folds dyn_ once it holds this many packets
+    static constexpr uint32_t kInlineMax = 3;     // segments this short are walked by the chain op (emit_scan)
     // Level of snapshot rows: chunk ops run at level 1, the chain op that stores the snapshots at
     // level 2 (a short scan is one op, also placed at level 2).  Readers are assigned levels when
     // they read, before the scan is emitted, so the level is fixed up front.

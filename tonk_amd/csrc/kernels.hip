@@ -14,12 +14,6 @@
 #include "serve.h"
 
 #define TAMD_WAVES_PER_WG 4
-#ifndef TAMD_BITOP3
-#define TAMD_BITOP3 1  // three-input XORs as v_bitop3_b32 (mul_sel)
-#endif
-#ifndef TAMD_ROLL
-#define TAMD_ROLL 1  // rolling row loads in ACCR runs (run_accr)
-#endif
 
 typedef unsigned long long u64;
 
@@ -150,13 +144,9 @@ __device__ __forceinline__ Sel sel4(uint32_t x) {
 }
 // a ^ b ^ c in one gfx950 v_bitop3_b32 (truth table 0x96); the compiler emits two v_xor_b32.
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
-#if TAMD_BITOP3
     uint32_t r;
     asm("v_bitop3_b32 %0, %1, %2, %3 bitop3:0x96" : "=v"(r) : "v"(a), "v"(b), "v"(c));
     return r;
-#else
-    return a ^ b ^ c;
-#endif
 }
 __device__ __forceinline__ uint32_t mul_sel(const Sel& s, const PermT& p) {
     return xor3(__builtin_amdgcn_perm(p.t[1], p.t[0], s.s0), __builtin_amdgcn_perm(p.t[3], p.t[2], s.s1),
@@ -343,7 +333,7 @@ __device__ __forceinline__ void run_accr(const tamd_instr& a, const tamd_instr& 
         const uint32_t W = 253u * 48u;
         uint32_t t = vgpr(((199u * (col0 % 253u)) % 253u) * 48u);
         const uint32_t tstep = vgpr(((199u * (cstep % 253u)) % 253u) * 48u);
-        if (TAMD_ROLL && nw == 1u) {
+        if (nw == 1u) {
             // Rolling loads: the rows of the next batch half are loaded as soon as a half has been
             // combined, so a wave keeps 3-6 row loads in flight while it computes instead of
             // waiting a full memory round trip per batch (same registers as a plain batch).
@@ -549,76 +539,31 @@ __device__ __forceinline__ void run_accr(const tamd_instr& a, const tamd_instr& 
             }
             return perm_at(lds, (uint32_t)__builtin_amdgcn_readlane((int)gv, (int)(i & 63u)));
         };
-        if (TAMD_ROLL) {  // rolling loads over this wave's batches
-            roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
-                                             [&](uint32_t i, const LV<NH>& v) __attribute__((always_inline)) {
-                                                 a0 ^= lv_mul<NH>(v, row_tab(i));
-                                             });
-            return;
-        }
-        for (uint32_t e = 0; e < count; e += TAMD_RBATCH) {
-            if ((unit++ & (nw - 1u)) != wid) continue;
-            LV<NH> d[TAMD_RBATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q) d[q] = TAMD_RUN_ROW(q);
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q)
-                if (e + q < count) a0 ^= lv_mul<NH>(lv_keep<FULL, NH>(d[q], o, len, ox), row_tab(e + q));
-        }
+        // rolling loads over this wave's batches
+        roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
+                                         [&](uint32_t i, const LV<NH>& v) __attribute__((always_inline)) {
+                                             a0 ^= lv_mul<NH>(v, row_tab(i));
+                                         });
     } else if (mode == TAMD_R_CAUCHY) {
         // CauchyElement(p, col mod 64) = inv((col mod 64) ^ (p + 64)) (SiameseCommon.h:212-218)
         uint32_t col = vgpr(col0);
         const uint32_t cs = vgpr(cstep), px = vgpr(p + 64u);
-        const uint8_t* inv = (const uint8_t*)(lds + TAMD_LDS_INV);
-        if (TAMD_ROLL) {  // rolling loads over this wave's batches
-            roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
-                                             [&](uint32_t i, const LV<NH>& v) __attribute__((always_inline)) {
-                                                 // the perm tables of inv((col mod 64) ^ (p + 64)), one LDS lookup
-                                                 const uint32_t ti = TAMD_LDS_CINV - 512u + ((((col + i * cs) & 63u) ^ px) << 3);
-                                                 a0 ^= lv_mul<NH>(v, perm_at(lds, ti));
-                                             });
-            return;
-        }
-        for (uint32_t e = 0; e < count; e += TAMD_RBATCH) {
-            if ((unit++ & (nw - 1u)) != wid) {
-                col += cs * TAMD_RBATCH;
-                continue;
-            }
-            LV<NH> d[TAMD_RBATCH];
-            uint32_t c[TAMD_RBATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q) {
-                d[q] = TAMD_RUN_ROW(q);
-                c[q] = inv[(col & 63u) ^ px];
-                col += cs;
-            }
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q)
-                if (e + q < count) a0 ^= lv_mul<NH>(lv_keep<FULL, NH>(d[q], o, len, ox), perm_at(lds, c[q] * 8u));
-        }
+        // rolling loads over this wave's batches
+        roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
+                                         [&](uint32_t i, const LV<NH>& v) __attribute__((always_inline)) {
+                                             // the perm tables of inv((col mod 64) ^ (p + 64)), one LDS lookup
+                                             const uint32_t ti = TAMD_LDS_CINV - 512u + ((((col + i * cs) & 63u) ^ px) << 3);
+                                             a0 ^= lv_mul<NH>(v, perm_at(lds, ti));
+                                         });
     } else {
         const bool plain = p == 1u;
         const PermT cp = perm_at(lds, p * 8u);
-        if (TAMD_ROLL) {
-            // rolling loads over this wave's batches: the rows are summed as they arrive and the
-            // sum multiplied once (a parity row: p = 1, no multiply at all)
-            LV<NH> x = lv_zero<NH>();
-            roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
-                                             [&](uint32_t, const LV<NH>& v) __attribute__((always_inline)) { x ^= v; });
-            a0 ^= plain ? x : lv_mul<NH>(x, cp);
-            return;
-        }
-        for (uint32_t e = 0; e < count; e += TAMD_RBATCH) {
-            if ((unit++ & (nw - 1u)) != wid) continue;
-            LV<NH> d[TAMD_RBATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q) d[q] = TAMD_RUN_ROW(q);
-            LV<NH> x = lv_zero<NH>();
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q)
-                if (e + q < count) x ^= lv_keep<FULL, NH>(d[q], o, len, ox);
-            a0 ^= plain ? x : lv_mul<NH>(x, cp);  // one coefficient: sum the batch's rows, one product
-        }
+        // rolling loads over this wave's batches: the rows are summed as they arrive and the
+        // sum multiplied once (a parity row: p = 1, no multiply at all)
+        LV<NH> x = lv_zero<NH>();
+        roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
+                                         [&](uint32_t, const LV<NH>& v) __attribute__((always_inline)) { x ^= v; });
+        a0 ^= plain ? x : lv_mul<NH>(x, cp);
     }
 #undef TAMD_RUN_ROW
 #undef TAMD_RUN_LD

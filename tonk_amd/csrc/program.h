@@ -160,7 +160,9 @@ typedef struct tamd_segments {
     tamd_segment s[TAMD_MAX_SEGMENTS];
     uint32_t n;
     uint32_t flags;  // bit 0: items are taken class by class across the segments (the launch's
-                     // longest first), else segment by segment
+                     // longest first), else segment by segment.  The host always sets it: it
+                     // never sends 0, and the executor's segment-by-segment branch only remains
+                     // so that the kernels' instructions stay as they were measured.
 } tamd_segments;
 
 static inline uint32_t tamd_w0(uint32_t kind, uint32_t arg, uint32_t arg2 = 0) {

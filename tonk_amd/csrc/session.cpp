@@ -104,29 +104,23 @@ std::string device_cpulist(int device) {
 }
 
 // CPUs of the device's NUMA node (the PCI device's local_cpulist) that this process may run on,
-// one hardware thread per core, and of those this device's share (node_core_share);
-// TONK_AMD_AFFINITY=node keeps both SMT threads, =none returns nothing (no pinning).  The
+// one hardware thread per core, and of those this device's share (node_core_share).  The
 // control-plane threads run there so their stream state lives in the node next to the GPU.
 // Bench A/B on one box (40 steps, twice each): 224-227 GiB/s with one thread per core, 212-226
-// with the node's CPUs, 199-217 unpinned.
+// with both SMT threads of the node's cores, 199-217 unpinned.
 std::vector<int> device_local_cpus(int device) {
-    const char* mode = getenv("TONK_AMD_AFFINITY");
     std::vector<int> out;
-    if (mode && !strcmp(mode, "none")) return out;
     const std::string mine = device_cpulist(device);
     if (mine.empty()) return out;
     cpu_set_t allowed;
     CPU_ZERO(&allowed);
     if (sched_getaffinity(0, sizeof(allowed), &allowed) != 0) return out;
-    const bool one_per_core = !(mode && !strcmp(mode, "node"));
     for (int c : parse_cpulist(mine.c_str())) {
         if (!CPU_ISSET(c, &allowed)) continue;
-        if (one_per_core) {
-            char tp[128];
-            snprintf(tp, sizeof(tp), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c);
-            const std::vector<int> sib = parse_cpulist(read_line(tp).c_str());
-            if (!sib.empty() && sib[0] != c) continue;
-        }
+        char tp[128];
+        snprintf(tp, sizeof(tp), "/sys/devices/system/cpu/cpu%d/topology/thread_siblings_list", c);
+        const std::vector<int> sib = parse_cpulist(read_line(tp).c_str());
+        if (!sib.empty() && sib[0] != c) continue;
         out.push_back(c);
     }
     int n = 0;
@@ -171,8 +165,7 @@ std::vector<int> pick_idle(const std::vector<int>& share, const std::vector<uint
 }
 
 std::vector<int> idle_cpus(const std::vector<int>& share, size_t want) {
-    static const bool off = getenv("TONK_AMD_NO_IDLE_PICK") != nullptr;  // A/B switch
-    if (off || share.size() <= want) return share.size() > want ? std::vector<int>(share.begin(), share.begin() + want) : share;
+    if (share.size() <= want) return share;
     const std::vector<uint64_t> a = cpu_busy_jiffies();
     std::this_thread::sleep_for(std::chrono::milliseconds(50));
     const std::vector<uint64_t> b = cpu_busy_jiffies();
@@ -400,7 +393,6 @@ struct Session {
     std::condition_variable cv_start, cv_done;
     std::atomic<bool> main_sleeping{false};
     const std::function<void(size_t, size_t)>* job = nullptr;  // the pass being run (run_all)
-    std::atomic<size_t> next_item{0};
     std::atomic<bool> quit{false};
 
     ~Session() {
@@ -428,50 +420,40 @@ struct Session {
     std::vector<uint32_t> order;
     std::vector<double> stream_ms;
 
-    // Sticky mode (default): thread t first runs its own streams (s % T == t), longest first, so
-    // a stream's state stays in the same core's caches from step to step, then takes any stream
-    // still unclaimed, longest first.  Without it streams are handed out longest first only.
+    // Pool thread t first runs its own streams (s % T == t), longest first, so a stream's state
+    // stays in the same core's caches from step to step, then takes any stream still unclaimed,
+    // longest first.  A session without a pool runs the streams on the caller, longest first.
     std::vector<std::atomic<uint8_t>> claimed;
-    bool sticky_job = false;
     void drain(const std::function<void(size_t, size_t)>& f, size_t ti) {
-        if (sticky_job) {
-            // own streams longest first (by the previous pass), so what is left for others to
-            // steal at the end of a pass is a slow thread's shortest streams
-            static const bool own_fifo = getenv("TONK_AMD_OWN_FIFO") != nullptr;  // A/B switch (profiling)
-            const size_t T = threads.size(), n = streams.size();
-            if (own_fifo || order.empty()) {
-                for (size_t s = ti; s < n; s += T)
-                    if (!claimed[s].exchange(1)) f(s, ti);
-            } else {
-                for (size_t k = 0; k < n; ++k) {
-                    const size_t s = order[k];
-                    if (s % T == ti && !claimed[s].exchange(1)) f(s, ti);
-                }
-            }
-            for (size_t k = 0; k < n; ++k) {
-                const size_t s = order.empty() ? k : order[k];
-                if (!claimed[s].exchange(1)) f(s, ti);
-            }
+        const size_t T = threads.size(), n = streams.size();
+        if (T == 0) {
+            for (size_t k = 0; k < n; ++k) f(order.empty() ? k : order[k], ti);
             return;
         }
-        for (;;) {
-            const size_t i = next_item.fetch_add(1);
-            if (i >= streams.size()) break;
-            f(order.empty() ? i : order[i], ti);
+        // own streams longest first (by the previous pass), so what is left for others to
+        // steal at the end of a pass is a slow thread's shortest streams
+        if (order.empty()) {
+            for (size_t s = ti; s < n; s += T)
+                if (!claimed[s].exchange(1)) f(s, ti);
+        } else {
+            for (size_t k = 0; k < n; ++k) {
+                const size_t s = order[k];
+                if (s % T == ti && !claimed[s].exchange(1)) f(s, ti);
+            }
+        }
+        for (size_t k = 0; k < n; ++k) {
+            const size_t s = order.empty() ? k : order[k];
+            if (!claimed[s].exchange(1)) f(s, ti);
         }
     }
 
     // Workers spin on the job generation for a while before sleeping on the condition variable,
     // and the main thread spins for the end of a pass: a step is a few hundred microseconds, so
     // a futex wake-up of 16 threads (and of the main thread) per pass is a visible share of it.
-    // TONK_AMD_SPIN_US sets the spin window (0: always sleep); 100 us covers the caller's work
-    // between passes (launch + layout, ~0.05 ms) without keeping 16 spinning threads beside the
-    // caller for long (the job's CPU quota counts them).
-    static uint64_t spin_ns() {
-        static const uint64_t v = getenv("TONK_AMD_SPIN_US") ? 1000ull * strtoull(getenv("TONK_AMD_SPIN_US"), nullptr, 10)
-                                                            : 100000ull;
-        return v;
-    }
+    // The spin window of 100 us covers the caller's work between passes (launch + layout,
+    // ~0.05 ms) without keeping 16 spinning threads beside the caller for long (the job's CPU
+    // quota counts them).
+    static constexpr uint64_t kSpinNs = 100000;
     std::atomic<uint64_t> gen{0};
     std::atomic<size_t> left{0};
     std::atomic<int> sleepers{0};
@@ -480,13 +462,12 @@ struct Session {
         // A pool thread may launch the step's program (early launch): its HIP calls (events,
         // launches) must target the session's device, not device 0.
         dev.bind_thread();
-        // Each pool thread on a core of its own (with sticky streams its streams' state stays in
-        // that core's caches); TONK_AMD_PIN=set lets every thread float over the whole CPU set.
-        static const bool pin_set = getenv("TONK_AMD_PIN") && !strcmp(getenv("TONK_AMD_PIN"), "set");
+        // Each pool thread on a core of its own (its streams' state stays in that core's caches),
+        // or over the whole CPU set when that has fewer CPUs than the pool has threads.
         if (!cpus.empty()) {
             cpu_set_t set;
             CPU_ZERO(&set);
-            if (pin_set || cpus.size() < threads_wanted) {
+            if (cpus.size() < threads_wanted) {
                 for (int c : cpus) CPU_SET(c, &set);
             } else {
                 CPU_SET(cpus[ti % cpus.size()], &set);
@@ -496,7 +477,7 @@ struct Session {
         uint64_t seen = 0;
         for (;;) {
             if (gen.load(std::memory_order_acquire) == seen) {
-                const auto until = std::chrono::steady_clock::now() + std::chrono::nanoseconds(spin_ns());
+                const auto until = std::chrono::steady_clock::now() + std::chrono::nanoseconds(kSpinNs);
                 unsigned k = 0;
                 while (gen.load(std::memory_order_acquire) == seen) {
                     __builtin_ia32_pause();
@@ -522,17 +503,12 @@ struct Session {
 
     void run_all(const std::function<void(size_t, size_t)>& f) {
         if (fr_running) fr_drain();  // (the pool leaves the free-running loop first)
-        static const bool sticky = getenv("TONK_AMD_NO_STICKY") == nullptr;  // A/B switch (profiling)
-        next_item = 0;
-        sticky_job = sticky && !threads.empty();
-        if (sticky_job) {
-            if (claimed.size() != streams.size()) claimed = std::vector<std::atomic<uint8_t>>(streams.size());
-            for (auto& c : claimed) c.store(0, std::memory_order_relaxed);
-        }
         if (threads.empty()) {
             drain(f, 0);
             return;
         }
+        if (claimed.size() != streams.size()) claimed = std::vector<std::atomic<uint8_t>>(streams.size());
+        for (auto& c : claimed) c.store(0, std::memory_order_relaxed);
         job = &f;
         job_kind.store(0, std::memory_order_relaxed);
         left.store(threads.size(), std::memory_order_relaxed);
@@ -585,7 +561,9 @@ struct Session {
     std::atomic<int> job_kind{0};             // pool job: 0 run_all pass, 1 fr_loop
     std::atomic<bool> fr_stop{false};
     std::atomic<uint32_t> fr_published{0};
-    uint32_t fr_launched = 0, fr_ahead = 2;
+    uint32_t fr_launched = 0;
+    // (programs k .. k + fr_ahead are open at once: each needs its own FrProg, Part and slot)
+    static constexpr uint32_t fr_ahead = 2;
     uint64_t fr_next_epoch = 1;
     std::atomic<uint64_t> fr_released{0};     // completed epoch (rows freed up to it are reusable)
     std::mutex fr_mu;
@@ -633,7 +611,7 @@ struct Session {
     // behind.  Otherwise a stream of a thread in its group of 8 (neighbouring cores: the stream's
     // state is still in the shared L3), and beyond the group only a stream that holds up the
     // oldest unlaunched program: a stolen stream's state moves to another core's caches, which
-    // costs more than it saves unless the launch waits for it (TONK_AMD_STEAL=0: steal anything).
+    // costs more than it saves unless the launch waits for it.
     std::atomic<uint32_t> fr_launched_pub{0};
     int fr_pick(size_t ti) {
         const int best = fr_scan(ti);
@@ -647,20 +625,18 @@ struct Session {
     }
     // The stream fr_pick would take for thread ti (not claimed), or -1.
     int fr_scan(size_t ti) {
-        static const int steal_mode = getenv("TONK_AMD_STEAL") ? atoi(getenv("TONK_AMD_STEAL")) : 1;  // A/B
         const uint32_t pub = fr_published.load(std::memory_order_acquire);
         const uint32_t oldest = fr_launched_pub.load(std::memory_order_acquire);
         const size_t T = threads.size(), n = streams.size();
         const size_t group = ti / 8;
         for (int pass = 0; pass < 3; ++pass) {
-            if (pass == 1 && steal_mode == 0) continue;
             int best = -1;
             uint32_t bk = ~0u;
             for (size_t s = pass ? 0 : ti; s < n; s += pass ? 1 : T) {
                 if (pass == 1 && (s % T) / 8 != group) continue;
                 Stream& st = *streams[s];
                 const uint32_t k = st.next_step.load(std::memory_order_acquire);
-                if (pass == 2 && steal_mode != 0 && k != oldest) continue;
+                if (pass == 2 && k != oldest) continue;
                 if (k < pub && k < bk && !st.busy.load(std::memory_order_relaxed)) {
                     best = (int)s;
                     bk = k;
@@ -690,7 +666,7 @@ struct Session {
                        fr_launched_pub.load(std::memory_order_acquire) != seen_l ||
                        fr_handback.load(std::memory_order_acquire) != seen_h;
             };
-            const auto until = std::chrono::steady_clock::now() + std::chrono::nanoseconds(spin_ns());
+            const auto until = std::chrono::steady_clock::now() + std::chrono::nanoseconds(kSpinNs);
             unsigned k = 0;
             bool woke = false;
             while (!(woke = changed())) {
@@ -877,7 +853,7 @@ struct Session {
     //   2. (main) lay out the merged program, wait for a free staging slot
     //   3. copy each stream's ops into the pinned staging buffer, close the stream's epoch
     //   4. (main) upload the program and launch it level by level
-    // Deferred mode (the default with level pipelining): phase 3 of a program runs at the start
+    // Deferred mode (every session with level pipelining): phase 3 of a program runs at the start
     // of the NEXT step's phase 1, in the same per-stream job (the stream's closed program is
     // still in that core's caches), and the program is launched after it.  A step is then one
     // pass over the pool instead of two; the device runs one program behind the host, which
@@ -945,9 +921,7 @@ struct Session {
         }
     }
     void sort_order() {
-        static const bool lpt = getenv("TONK_AMD_STREAM_FIFO") == nullptr;  // A/B switch (profiling)
-        if (lpt)
-            std::sort(order.begin(), order.end(), [this](uint32_t a, uint32_t b) { return stream_ms[a] > stream_ms[b]; });
+        std::sort(order.begin(), order.end(), [this](uint32_t a, uint32_t b) { return stream_ms[a] > stream_ms[b]; });
     }
     void account_busy() {
         double mx = 0;
@@ -973,22 +947,17 @@ struct Session {
         std::fill(fill_ms.begin(), fill_ms.end(), 0.0);
         init_order();
         const bool fill = have_closed;
-        // Early launch: the thread that fills the last stream launches the program at once
-        // (the other threads only run control planes, which touch no device state) instead of the
-        // caller after the pass.  Record mode runs the same schedule (its digests are enqueued by
-        // the launches themselves).
-        // A session without workers runs the same order: its one stream's previous program is
-        // filled and launched before this step's control plane, which then overlaps its levels.
-        static const bool early_ok = getenv("TONK_AMD_LATE_LAUNCH") == nullptr;  // A/B switch
-        const bool early = fill && early_ok;
-        if (early) fills_left.store(streams.size(), std::memory_order_relaxed);
-        run_all([this, originals, finish, rel, fill, early, &ms](size_t i, size_t ti) {
+        // Early launch: the program is launched as soon as its last stream is filled, not after
+        // the pass, so the control planes that follow overlap its levels.  Record mode runs the
+        // same schedule (its digests are enqueued by the launches themselves).
+        if (fill) fills_left.store(streams.size(), std::memory_order_relaxed);
+        run_all([this, originals, finish, rel, fill, &ms](size_t i, size_t ti) {
             const auto w0 = clk::now();
             Context& c = *ctxs[i];
             if (fill) {
                 dev.fill(i);
                 fill_ms[ti] += ms(w0, clk::now());
-                if (early && fills_left.fetch_sub(1, std::memory_order_acq_rel) == 1) launch_closed();
+                if (fills_left.fetch_sub(1, std::memory_order_acq_rel) == 1) launch_closed();
             }
             c.rows.release_up_to(rel);
             streams[i]->clock = clock_msec;
@@ -1004,7 +973,6 @@ struct Session {
         const auto t1 = clk::now();
         account_busy();
         for (double f : fill_ms) host_ms[3] += f / (double)fill_ms.size();
-        if (fill && !early) launch_closed();
         const auto t2 = clk::now();
         std::vector<Context*> cs;
         for (auto& c : ctxs) cs.push_back(c.get());
@@ -1176,9 +1144,9 @@ void* tamd_session_create(const tamd_session_params* p, char* err, size_t err_le
     std::unique_ptr<Session> s(new Session());
     s->prm = *p;
     // Level pipelining (Device::set_pipelined): off when packets are staged through the host
-    // (the D2H gather right after a program needs all of its levels) and for A/B runs.  A
-    // program stays in flight for as many launches as it has levels: 6 staging slots.
-    const bool pipe = !p->stage_host && getenv("TONK_AMD_NO_PIPELINE") == nullptr;
+    // (the D2H gather right after a program needs all of its levels).  A program stays in flight
+    // for as many launches as it has levels: 6 staging slots.
+    const bool pipe = !p->stage_host;
     uint32_t nthreads = p->n_threads ? (p->n_threads < p->n_streams ? p->n_threads : p->n_streams) : 1;
     // The worker pool's cores: this GPU's share of its NUMA node (device_local_cpus).  A share
     // smaller than the pool (a node with fewer usable cores per GPU than workers) shrinks the pool
@@ -1191,29 +1159,19 @@ void* tamd_session_create(const tamd_session_params* p, char* err, size_t err_le
     }
     // The free-running schedule (worker threads, pipelined levels): programs assembled in
     // parallel (Device::add_part) in 8 slots -- up to fr_ahead open, the rest in flight; otherwise
-    // one laid-out program per step in 6 slots (TONK_AMD_PASSES=1 keeps the pass schedule).
-    // TONK_AMD_FR_SINGLE=1 runs it for one-thread sessions too (one worker beside the caller:
-    // the worker's control plane of step k + 1 overlaps the caller's assembly and launch of
-    // program k).  Off by default: on the decoder-stress stream the worker's control plane ran
-    // 25-40 % slower than the caller's own (configs[4]: 2.8 vs 3.6 GiB/s at 512 originals per
-    // program, 3.6 vs 4.2 at 1024), which costs more than the overlap gains.
-    static const bool fr_single = getenv("TONK_AMD_FR_SINGLE") != nullptr;
-    s->fr_mode = pipe && (nthreads > 1 || fr_single) && getenv("TONK_AMD_NO_DEFER") == nullptr &&
-                 getenv("TONK_AMD_PASSES") == nullptr;
-    if (const char* a = getenv("TONK_AMD_RUNAHEAD")) {
-        // (programs k .. k + fr_ahead are open at once: each needs its own FrProg, Part and slot)
-        const int v = atoi(a);
-        s->fr_ahead = v < 1 ? 1u : v > (int)Session::kFrRing - 1 ? Session::kFrRing - 1 : (uint32_t)v;
-    }
+    // one laid-out program per step in 6 slots.  One-thread sessions keep the latter: with one
+    // worker beside the caller (its control plane of step k + 1 overlapping the caller's assembly
+    // and launch of program k), the worker's control plane ran 25-40 % slower on the
+    // decoder-stress stream than the caller's own (configs[4]: 2.8 vs 3.6 GiB/s at 512 originals
+    // per program, 3.6 vs 4.2 at 1024), which costs more than the overlap gains.
+    s->fr_mode = pipe && nthreads > 1;
     s->dev.set_small_uploads(p->n_streams <= 4);
     if (s->fr_mode) s->dev.set_assembly_slots(8, p->n_streams <= 4 ? 8 : 24);
     else {
-        // (TONK_AMD_SLOTS: A/B knob for the slot count of the pass schedule)
         // (few streams: a program's levels stay in flight until later programs launch beside
         // them; with 6 slots a decoder-stress stream's deep programs drained the device for a slot
         // every program: configs[4] 5.50 -> 5.83 GiB/s with 12)
-        const size_t slots = getenv("TONK_AMD_SLOTS") ? (size_t)atoi(getenv("TONK_AMD_SLOTS"))
-                                                      : (pipe ? (p->n_streams <= 4 ? 12 : 6) : 2);
+        const size_t slots = pipe ? (p->n_streams <= 4 ? 12 : 6) : 2;
         s->dev.set_program_slots(slots, (p->n_streams <= 4 ? 2u : 16u) << 20);
     }
     if (!s->dev.init((int)p->device, p->arena_bytes)) return fail(s->dev.error());
@@ -1224,9 +1182,9 @@ void* tamd_session_create(const tamd_session_params* p, char* err, size_t err_le
     s->row_cap = ((p->payload_max + 4 + 63) / 64) * 64;
     s->busy_ms.assign(nthreads, 0.0);
     s->fill_ms.assign(nthreads, 0.0);
-    s->deferred = pipe && getenv("TONK_AMD_NO_DEFER") == nullptr;
+    s->deferred = pipe;
     Session* raw = s.get();
-    if (nthreads > 1 || s->fr_mode) {
+    if (nthreads > 1) {
         raw->cpus = idle_cpus(share.empty() ? device_local_cpus((int)p->device) : share, nthreads);
         raw->threads_wanted = nthreads;
         for (uint32_t t = 0; t < nthreads; ++t) raw->threads.emplace_back([raw, t] { raw->pool_loop(t); });
@@ -1243,25 +1201,18 @@ void* tamd_session_create(const tamd_session_params* p, char* err, size_t err_le
         // grows with the solves per program and sets the host time (configs[4] decoder stress:
         // 1.84 -> 3.63 GiB/s).  Batched sessions keep inlining: there the extra levels are extra
         // full-width launches (configs[3]: 33 -> 57 launches per 30 steps, device time per step
-        // +11 %, no host gain).  TONK_AMD_EXPAND=<terms> overrides (A/B knob).
-        static const char* expand_env = getenv("TONK_AMD_EXPAND");
-        const uint32_t expand = expand_env ? (uint32_t)atoi(expand_env) : (p->n_streams <= 4 ? 16u : ~0u);
-        if (pipe) ctx->ex.expand_limit = expand;
+        // +11 %, no host gain).
+        if (pipe) ctx->ex.expand_limit = p->n_streams <= 4 ? 16u : ~0u;
         // The same split for back substitution over materialized rows (configs[4]: host time per
         // program -12 %, device -6 %; configs[2]/[3]: +1 level, +20 % launches, no fewer bytes).
-        // TONK_AMD_BACKSUB_ROWS=<unknowns> overrides (A/B knob).
-        static const char* bs_env = getenv("TONK_AMD_BACKSUB_ROWS");
-        ctx->backsub_rows = bs_env ? (uint32_t)atoi(bs_env) : (p->n_streams <= 4 ? 2u : ~0u);
-        // (TONK_AMD_DENSE_SPLIT=<packets> overrides: A/B knob)
-        static const char* split_env = getenv("TONK_AMD_DENSE_SPLIT");
-        ctx->dense_split = split_env ? (uint32_t)atoi(split_env) : (p->n_streams <= 4 ? 0u : Encoder::kDenseSplit);
+        ctx->backsub_rows = p->n_streams <= 4 ? 2u : ~0u;
+        ctx->dense_split = p->n_streams <= 4 ? 0u : Encoder::kDenseSplit;
         // Few-stream sessions also take the C ABI's lane scan levels (Context::short_scans): a
         // snapshot read while its scan is one op long is promised level 1, which takes a level off
         // configs[1]'s program (4 -> 3 launches, 17.4 -> 19.3 GiB/s; configs[4] 5.9 -> 6.2).
         // Batched sessions keep the chain level: a promised snapshot makes its whole scan one op,
-        // a long item in a full-width launch.  TONK_AMD_SHORT_SCANS=0|1 overrides (A/B knob).
-        static const char* short_env = getenv("TONK_AMD_SHORT_SCANS");
-        ctx->short_scans = short_env ? atoi(short_env) != 0 : p->n_streams <= 4;
+        // a long item in a full-width launch.
+        ctx->short_scans = p->n_streams <= 4;
         std::unique_ptr<Stream> st(new Stream());
         st->ctx = ctx.get();
         wl::Params& q = st->p;
@@ -1282,7 +1233,6 @@ void* tamd_session_create(const tamd_session_params* p, char* err, size_t err_le
         q.rtx_every = p->rtx_every;
         q.rtx_msec = p->rtx_msec ? p->rtx_msec : 1;
         q.hold_full = p->hold_full;
-        q.batch_adds = getenv("TONK_AMD_SINGLE_ADDS") ? 0 : 1;  // A/B switch (profiling)
         q.seed_data = 1000 + q.stream_id;
         q.seed_loss = 2000 + q.stream_id;
         st->enc.reset(new Encoder(ctx.get(), raw->row_cap));
