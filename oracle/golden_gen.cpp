@@ -212,27 +212,25 @@ struct RefTranscript {
     bool enabled = true;
     void on_encode(int rc, const RefBackend::RecRef& r) {
         if (!enabled) return;
-        if (rc != 0) { t.put("E %d\n", rc); return; }
+        if (rc != 0) return fmt_encode_error(t, rc);
         RecoveryMetadataView m;
         decode_footer(r.bytes, m);
-        t.put("E 0 %zu %u %u %u %u %016llx\n", r.bytes.size(), m.row, m.cs, m.sc, m.ldpc,
-              (unsigned long long)fnv1a(r.bytes.data(), r.bytes.size()));
+        fmt_encode(t, r.bytes.size(), m.row, m.cs, m.sc, m.ldpc, fnv1a(r.bytes.data(), r.bytes.size()));
     }
     void on_decode(int rc, const std::vector<uint32_t>& nums, const RefBackend::DecRef& d) {
         if (!enabled) return;
-        t.put("D %d %zu", rc, nums.size());
-        for (size_t k = 0; k < nums.size(); ++k)
-            t.put(" %u:%zu:%016llx", nums[k], d.data[k].size(),
-                  (unsigned long long)fnv1a(d.data[k].data(), d.data[k].size()));
+        fmt_decode_head(t, rc, nums.size());
+        for (size_t k = 0; k < nums.size(); ++k) {
+            fmt_decode_entry(t, nums[k]);
+            fmt_decode_digest(t, d.data[k].size(), fnv1a(d.data[k].data(), d.data[k].size()));
+        }
         t.put("\n");
     }
     void on_ack(int rd, const uint8_t* buf, uint32_t used, int re, uint32_t next) {
-        if (!enabled) return;
-        t.put("K %d %u %016llx %d %u\n", rd, used, (unsigned long long)fnv1a(buf, used), re, next);
+        if (enabled) fmt_ack(t, rd, buf, used, re, next);
     }
     void on_event(char kind, int rc, uint32_t a, uint32_t b) {
-        if (!enabled) return;
-        if (rc != 0) t.put("%c %d %u %u\n", kind, rc, a, b);
+        if (enabled) fmt_event(t, kind, rc, a, b);
     }
     void on_retransmit(int rc, uint32_t num, uint32_t bytes, uint64_t h) {
         if (enabled) fmt_retransmit(t, rc, num, bytes, h);

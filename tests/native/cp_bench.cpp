@@ -1,11 +1,10 @@
 // cp_bench.cpp -- TEST/PROFILING ONLY.  Host control-plane cost of the bench workload with no
-// device: the same backend the session uses (device rows are just handles; programs are built
-// and then dropped).  Reports ns per original per thread; build with -pg for gprof.
+// device: the backend the session's streams run (resident_backend.h; device rows are just
+// handles; programs are built and then dropped).  Reports ns per original per thread; build with
+// -pg for gprof.
 //
 // usage: cp_bench streams=S n=N step=K [workload keys]
-#include "../../tonk_amd/csrc/decoder.h"
-#include "../../tonk_amd/csrc/workload.h"
-#include "../../tonk_amd/csrc/prof.h"
+#include "resident_streams.h"
 
 #include <chrono>
 #include <x86intrin.h>
@@ -34,88 +33,24 @@ const char* const names[kSlots] = {"enc_add", "enc_encode", "enc_ack", "dec_add_
 } }
 #endif
 
+// stub=1: encoder calls return at once; stub=2: decoder calls too (what is left is the runner)
 static int g_stub = 0;
-static int g_nobatch = 0;
-static int g_pipe = 1;
-static bool g_contig = true;  // contig=0: the codecs check run contiguity themselves (rows are allocated in order)
-static uint64_t g_step_clock = 1000;  // nobatch=1: single adds only (the runner's fallback path)  // stub=1: encoder calls return at once; stub=2: decoder calls too
-struct Null {
-    struct RecRef { RecoveryOut out; };
-    struct DecRef {};
-    Context* ctx;
-    Encoder* enc;
-    Decoder* dec;
-    std::vector<RowId> enc_rows, dec_rows;
-    uint64_t instrs = 0;
-    // (rows are allocated in order per side: each side's offsets are affine)
-    uint32_t pool = 0;  // rows per side; original i uses row i mod pool
-    uint64_t layout(const std::vector<RowId>& rows, uint32_t index, uint32_t k) const {
-        if (index % pool + k > pool) return 0;
-        const uint32_t o0 = ctx->rows.offset(rows[0]), stride = ctx->rows.offset(rows[1]) - o0;
-        return (uint64_t)(o0 + (index % pool) * stride) << 32 | stride;
-    }
+struct Stubbed : ResidentBackend {
     int enc_add(uint32_t index, uint32_t len, uint32_t* col) {
-        const uint32_t hb = length_header_bytes(len);
-        TAMD_PROF_SCOPE(kEncAdd);
         if (g_stub) { *col = index; return 0; }
-        return enc->add(enc_rows[index], hb + len, hb, len, nullptr, col, true);
+        return ResidentBackend::enc_add(index, len, col);
     }
     bool enc_add_run(uint32_t index, uint32_t k, uint32_t len, uint32_t* col0) {
-        if (g_stub || g_nobatch) return false;
-        const uint32_t hb = length_header_bytes(len);
-        TAMD_PROF_SCOPE(kEncAdd);
-        return enc->add_run(&enc_rows[index], k, hb + len, hb, len, true, col0, g_contig ? layout(enc_rows, index, k) : 0);
+        return !g_stub && ResidentBackend::enc_add_run(index, k, len, col0);
     }
     bool dec_add_run(uint32_t col0, uint32_t index, uint32_t k, uint32_t len) {
-        if (g_stub > 1 || g_nobatch) return false;
-        const uint32_t hb = length_header_bytes(len);
-        TAMD_PROF_SCOPE(kDecAddOrig);
-        return dec->add_run_inorder(col0, &dec_rows[index], k, hb + len, hb, len, true, g_contig ? layout(dec_rows, index, k) : 0);
+        return g_stub <= 1 && ResidentBackend::dec_add_run(col0, index, k, len);
     }
-    int enc_encode(RecRef& r) { TAMD_PROF_SCOPE(kEncEncode); if (g_stub) return 2; return enc->encode(r.out); }
-    int enc_ack(const uint8_t* b, uint32_t n, uint32_t* next) { TAMD_PROF_SCOPE(kEncAck); return enc->acknowledge(b, n, next); }
-    int enc_is_ready() { return enc->remaining_slots() <= 2 ? (int)kMaxPacketsReached : 0; }
+    int enc_encode(RecRef& r) { return g_stub ? 2 : ResidentBackend::enc_encode(r); }
     int dec_add_original(uint32_t col, uint32_t index, uint32_t len) {
-        const uint32_t hb = length_header_bytes(len);
-        TAMD_PROF_SCOPE(kDecAddOrig);
-        if (g_stub > 1) return 0;
-        bool took = false;
-        const int r = dec->add_original(col, dec_rows[index], hb + len, hb, len, nullptr, &took, true);
-        return r;
+        return g_stub > 1 ? 0 : ResidentBackend::dec_add_original(col, index, len);
     }
-    void recovery_lost(const RecRef& r) { ctx->rows.free_deferred(r.out.row); }
-    int dec_add_recovery(const RecRef& r) {
-        uint8_t tail[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const uint32_t tl = r.out.total() < 8 ? r.out.total() : 8;
-        memcpy(tail + tl - r.out.footer_len, r.out.footer, r.out.footer_len);
-        TAMD_PROF_SCOPE(kDecAddRec);
-        bool took = false;
-        const int rc = dec->add_recovery(r.out.row, r.out.total(), tail, nullptr, &took);
-        if (!took) ctx->rows.free_deferred(r.out.row);
-        return rc;
-    }
-    int dec_is_ready() { TAMD_PROF_SCOPE(kDecIsReady); if (g_stub > 1) return 2; return dec->is_ready(); }
-    std::vector<RecoveredPacket*> got;
-    int dec_decode(std::vector<uint32_t>& nums, DecRef&) {
-        TAMD_PROF_SCOPE(kDecDecode);
-        got.clear();
-        const int rc = dec->decode(got);
-        if (rc == 0) for (auto* p : got) nums.push_back(p->packet_num);
-        return rc;
-    }
-    int dec_ack(uint8_t* b, uint32_t l, uint32_t* u) { TAMD_PROF_SCOPE(kDecAck); return dec->ack(b, l, u); }
-    void stats(uint64_t e[9], uint64_t d[11]) { enc->stats(e, 9); dec->stats(d, 11); }
-    void set_time(uint64_t) {}
-    int enc_retransmit(uint32_t*, uint32_t*, const uint8_t**) { return 2; }
-};
-
-struct NoTr {
-    void on_encode(int, const Null::RecRef&) {}
-    void on_decode(int, const std::vector<uint32_t>&, const Null::DecRef&) {}
-    void on_ack(int, const uint8_t*, uint32_t, int, uint32_t) {}
-    void on_event(char, int, uint32_t, uint32_t) {}
-    void on_stats(const uint64_t*, const uint64_t*) {}
-    void on_retransmit(int, uint32_t, uint32_t, uint64_t) {}
+    int dec_is_ready() { return g_stub > 1 ? 2 : ResidentBackend::dec_is_ready(); }
 };
 
 // Poor man's sampling profiler (no perf in the container): SIGPROF every 100 us of CPU time
@@ -304,46 +239,34 @@ int main(int argc, char** argv) {
     for (int i = 1; i < argc; ++i)
         if (!strncmp(argv[i], "sample=", 7)) sample_out = argv[i] + 7;
     gf_init();
-    wl::Params p;
-    p.loss_thresh = 42949673;
-    p.fec_rate_q16 = 1311;
-    p.ack_every = 64;
-    uint32_t streams = 8, step = 4096, warm_steps = 0, expand = ~0u, backsub = ~0u, reps = 1;  // warm: untimed, unsampled first steps
-    p.n_originals = 4096 * 6;
+    ResidentArgs args;
+    if (getenv("TONK_AMD_DENSE_SPLIT")) args.dense_split = atoi(getenv("TONK_AMD_DENSE_SPLIT"));
+    uint32_t warm_steps = 0, reps = 1;  // warm: untimed, unsampled first steps
     for (int i = 1; i < argc; ++i) {
         const char* eq = strchr(argv[i], '=');
-        if (!eq) continue;
-        std::string k(argv[i], eq - argv[i]);
-        if (k == "sample") continue;
-        if (k == "stub") { g_stub = atoi(eq + 1); continue; }
-        if (k == "nobatch") { g_nobatch = atoi(eq + 1); continue; }
-        if (k == "warm") { warm_steps = (uint32_t)atoi(eq + 1); continue; }
-        if (k == "expand") { expand = (uint32_t)strtoul(eq + 1, nullptr, 0); continue; }
-        if (k == "backsub") { backsub = (uint32_t)strtoul(eq + 1, nullptr, 0); continue; }
-        if (k == "pipe") { g_pipe = atoi(eq + 1); continue; }
-        if (k == "contig") { g_contig = atoi(eq + 1) != 0; continue; }
-        if (k == "reps") { reps = (uint32_t)atoi(eq + 1); continue; }  // level pipelining as the session runs it
-        if (k == "prefault") {  // MB of heap faulted in and kept before the run (cold-start studies)
-            const size_t mb = (size_t)atoi(eq + 1);
+        const std::string k(argv[i], eq ? eq - argv[i] : 0);
+        const unsigned long long v = eq ? strtoull(eq + 1, nullptr, 0) : 0;
+        if (k == "sample" || k == "list") continue;  // (sample: read above; list: prog_digest's, so one argument list serves both)
+        else if (k == "stub") g_stub = (int)v;
+        else if (k == "warm") warm_steps = (uint32_t)v;
+        else if (k == "expand") args.expand = (uint32_t)v;
+        else if (k == "backsub") args.backsub = (uint32_t)v;
+        else if (k == "pipe") args.pipeline = v != 0;  // level pipelining as the session runs it
+        else if (k == "reps") reps = (uint32_t)v;
+        else if (k == "prefault") {  // MB of heap faulted in and kept before the run (cold-start studies)
             mallopt(M_MMAP_THRESHOLD, 512 << 20);
             mallopt(M_TRIM_THRESHOLD, 1 << 30);
-            void* m = malloc(mb << 20);
-            if (m) memset(m, 1, mb << 20);
+            void* m = malloc((size_t)v << 20);
+            if (m) memset(m, 1, (size_t)v << 20);
             free(m);
-            continue;
+        } else if (!args.parse(k, v)) {
+            fprintf(stderr, "cp_bench: unknown key %s\n", argv[i]);
+            return 2;
         }
-        const unsigned long long v = strtoull(eq + 1, nullptr, 0);
-        if (k == "streams") streams = (uint32_t)v;
-        else if (k == "n") p.n_originals = (uint32_t)v;
-        else if (k == "step") step = (uint32_t)v;
-        else if (k == "loss") p.loss_thresh = (uint32_t)v;
-        else if (k == "fec") p.fec_rate_q16 = (uint32_t)v;
-        else if (k == "ack") p.ack_every = (uint32_t)v;
-        else if (k == "ge") p.ge_enable = (uint32_t)v;
-        else if (k == "gb") p.gb_thresh = (uint32_t)v;
-        else if (k == "bg") p.bg_thresh = (uint32_t)v;
-        else if (k == "arq") p.arq_lag = (uint32_t)v;
     }
+    const wl::Params& p = args.p;
+    const uint32_t streams = args.streams, step = args.step;
+    if (!streams || !step || !p.n_originals) return 2;
     // reps=R: the whole run is repeated R times with fresh codecs; every (step, stream) segment
     // is timed (TSC) and the sum over segments of each segment's minimum over the repetitions is
     // reported (segmin_cyc_per_original): a host-load burst inflates one repetition's segment,
@@ -362,41 +285,9 @@ int main(int argc, char** argv) {
     for (uint32_t rep = 0; rep < reps; ++rep) {
     // One Context per stream with each side's input rows contiguous, as the session lays them out
     // (tamd_session_generate), and steps of `step` originals per stream.
-    std::vector<std::unique_ptr<Context>> ctxs(streams);
-    std::vector<std::unique_ptr<Null>> be(streams);
-    std::vector<std::unique_ptr<Encoder>> encs(streams);
-    std::vector<std::unique_ptr<Decoder>> decs(streams);
-    std::vector<wl::Params> ps(streams, p);
-    NoTr tr;
-    std::vector<std::unique_ptr<wl::Runner<Null, NoTr>>> run(streams);
-    for (uint32_t s = 0; s < streams; ++s) {
-        ps[s].seed_data = 1000 + s;
-        ps[s].seed_loss = 2000 + s;
-        ctxs[s].reset(new Context());
-        Context& ctx = *ctxs[s];
-        ctx.ex.expand_limit = expand;
-        ctx.backsub_rows = backsub;
-        ctx.dense_split = getenv("TONK_AMD_DENSE_SPLIT") ? (uint32_t)atoi(getenv("TONK_AMD_DENSE_SPLIT"))
-                                                        : (streams > 4 ? Encoder::kDenseSplit : 0u);
-        ctx.pipeline = g_pipe != 0;
-        ctx.rows.init(4ull * std::min<uint32_t>(p.n_originals, 65536) * 1344 + (256u << 20));
-        encs[s].reset(new Encoder(&ctx, 1344));
-        encs[s]->set_clock(&g_step_clock);  // the session reads the clock once per step
-        decs[s].reset(new Decoder(&ctx, 1344));
-        be[s].reset(new Null());
-        be[s]->ctx = &ctx;
-        be[s]->enc = encs[s].get();
-        be[s]->dec = decs[s].get();
-        // (a pool of 65536 rows per side, as the bench's sessions: long runs fit in memory)
-        const uint32_t pool = std::min<uint32_t>(p.n_originals, 65536);
-        be[s]->pool = pool;
-        for (uint32_t i = 0; i < pool; ++i) be[s]->enc_rows.push_back(ctx.rows.alloc(1302));
-        for (uint32_t i = 0; i < pool; ++i) be[s]->dec_rows.push_back(ctx.rows.alloc(1302));
-        for (uint32_t i = pool; i < p.n_originals; ++i) be[s]->enc_rows.push_back(be[s]->enc_rows[i - pool]);
-        for (uint32_t i = pool; i < p.n_originals; ++i) be[s]->dec_rows.push_back(be[s]->dec_rows[i - pool]);
-        run[s].reset(new wl::Runner<Null, NoTr>(ps[s], *be[s], tr));
-        run[s]->pregenerate();
-    }
+    ResidentStreams<Stubbed> rs(args);
+    auto& ctxs = rs.ctxs;
+    auto& run = rs.run;
     instrs = ops = acc_bytes = store_bytes = 0;
     timed_originals = 0;
     auto start_sampling = [&]() {
@@ -460,7 +351,7 @@ int main(int argc, char** argv) {
         }
     }
     g_sampling = 0;
-    last_enc_window = (unsigned)(kMaxPackets - encs[0]->remaining_slots());
+    last_enc_window = (unsigned)(kMaxPackets - rs.be[0]->enc->remaining_slots());
     }  // rep
     const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     const double cpu_sec = cpu_now() - c0;

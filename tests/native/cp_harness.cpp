@@ -177,13 +177,7 @@ struct Harness {
         return b;
     }
 
-    // transcript entries waiting for their rows to be computed
-    struct PendEnc { RowId row; uint32_t total; RecoveryMeta meta; size_t pos; };
-    struct PendDec { RowId row; uint32_t upper; size_t pos; };
-    std::vector<PendEnc> pend_enc;
-    std::vector<std::vector<PendDec>> pend_dec;  // per decode line
-    std::vector<size_t> pend_dec_pos;
-    std::vector<std::string> lines;  // transcript lines, some filled after execution
+    DeferredTranscript tr;  // transcript lines, some filled after execution (resolve)
 
     explicit Harness(const Params& prm) : p(prm) {
         row_bytes = ((p.payload_max + 4 + 8 + 63) / 64) * 64;
@@ -363,31 +357,17 @@ struct Harness {
     }
 
     void resolve() {
-        char buf[256];
-        for (const PendEnc& e : pend_enc) {
-            const uint8_t* d = at(e.row);
-            snprintf(buf, sizeof(buf), "E 0 %u %u %u %u %u %016llx", e.total, e.meta.Row, e.meta.ColumnStart,
-                     e.meta.SumCount, e.meta.LDPCCount, (unsigned long long)fnv1a(d, e.total));
-            lines[e.pos] = buf;
+        for (size_t k = 0; k < tr.pend_enc.size(); ++k)
+            tr.resolve_enc(k, fnv1a(at(tr.pend_enc[k].row), tr.pend_enc[k].total));
+        for (size_t k = 0; k < tr.pend_dec.size(); ++k) {
+            const DeferredTranscript::Dec& dd = tr.pend_dec[k];
+            const uint8_t* d = at(dd.row);
+            unsigned len = 0;
+            const int hb = get_length_header(d, dd.upper, len);
+            if (hb < 1 || len + hb > dd.upper) { if (error.empty()) error = "bad recovered header"; continue; }
+            tr.resolve_dec(k, len, fnv1a(d + hb, len));
         }
-        pend_enc.clear();
-        for (size_t k = 0; k < pend_dec.size(); ++k) {
-            std::string& ln = lines[pend_dec_pos[k]];
-            for (const PendDec& dd : pend_dec[k]) {
-                const uint8_t* d = at(dd.row);
-                unsigned len = 0;
-                const int hb = get_length_header(d, dd.upper, len);
-                uint32_t packet = 0;
-                if (hb < 1 || len + hb > dd.upper) { if (error.empty()) error = "bad recovered header"; continue; }
-                (void)packet;
-                snprintf(buf, sizeof(buf), ":%u:%016llx", len, (unsigned long long)fnv1a(d + hb, len));
-                // placeholder "#" marks where the length/hash go
-                const size_t at_pos = ln.find('#');
-                if (at_pos != std::string::npos) ln.replace(at_pos, 1, buf);
-            }
-        }
-        pend_dec.clear();
-        pend_dec_pos.clear();
+        tr.resolved();
     }
 
     // ---- backend interface for run_stream ----
@@ -539,10 +519,9 @@ struct Harness {
             rc = D()->decode(got);
         }
         if (rc == kSuccess) {
-            pend_dec.emplace_back();
             for (RecoveredPacket* rp : got) {
                 nums.push_back(rp->packet_num);
-                pend_dec.back().push_back(PendDec{rp->row, rp->framed_upper, 0});
+                tr.recovered(rp->row, rp->framed_upper);
             }
         }
         return rc;
@@ -573,42 +552,20 @@ struct Harness {
 
     // ---- transcript interface ----
     void on_encode(int rc, const RecRef& r) {
-        if (rc != 0) { lines.push_back("E " + std::to_string(rc)); return; }
-        pend_enc.push_back(PendEnc{r.out.row, r.out.total(), r.out.meta, lines.size()});
-        lines.push_back("E ?");
-        if (sync) flush();
+        tr.encode(rc, r.out.row, r.out.total(), r.out.meta.Row, r.out.meta.ColumnStart, r.out.meta.SumCount,
+                  r.out.meta.LDPCCount);
+        if (rc == 0 && sync) flush();
     }
     void on_decode(int rc, const std::vector<uint32_t>& nums, const DecRef&) {
-        std::string ln = "D " + std::to_string(rc) + " " + std::to_string(nums.size());
-        for (uint32_t n : nums) ln += " " + std::to_string(n) + "#";
-        if (rc == 0) pend_dec_pos.push_back(lines.size());
-        lines.push_back(ln);
+        tr.decode(rc, nums);
         if (sync) flush();
     }
-    void on_ack(int rd, const uint8_t* buf, uint32_t used, int re, uint32_t next) {
-        char b[128];
-        snprintf(b, sizeof(b), "K %d %u %016llx %d %u", rd, used, (unsigned long long)fnv1a(buf, used), re, next);
-        lines.push_back(b);
-    }
-    void on_event(char kind, int rc, uint32_t a, uint32_t b) {
-        if (rc == 0) return;
-        char t[64];
-        snprintf(t, sizeof(t), "%c %d %u %u", kind, rc, a, b);
-        lines.push_back(t);
-    }
-    void on_retransmit(int rc, uint32_t num, uint32_t bytes, uint64_t h) {
-        TextSink t;
-        fmt_retransmit(t, rc, num, bytes, h);
-        t.text.pop_back();
-        lines.push_back(t.text);
-    }
+    void on_ack(int rd, const uint8_t* buf, uint32_t used, int re, uint32_t next) { tr.ack(rd, buf, used, re, next); }
+    void on_event(char kind, int rc, uint32_t a, uint32_t b) { tr.event(kind, rc, a, b); }
+    void on_retransmit(int rc, uint32_t num, uint32_t bytes, uint64_t h) { tr.retransmit(rc, num, bytes, h); }
     void on_stats(const uint64_t e[9], const uint64_t d[11]) {
         flush();
-        TextSink t;
-        fmt_stats(t, e, d);
-        std::string s = t.text;
-        if (!s.empty() && s.back() == '\n') s.pop_back();
-        lines.push_back(s);
+        tr.stats(e, d);
     }
 };
 
@@ -649,7 +606,7 @@ int main(int argc, char** argv) {
     h.flush();
     FILE* f = fopen(argv[1], "wb");
     if (!f) return 4;
-    for (const std::string& l : h.lines) fprintf(f, "%s\n", l.c_str());
+    for (const std::string& l : h.tr.lines) fprintf(f, "%s\n", l.c_str());
     fprintf(f, "Z originals=%llu lost=%llu recoveries=%llu lostrec=%llu recovered=%llu arq=%llu "
                "acks=%llu decodes=%llu flush=%llu missing=%llu bad=0\n",
             (unsigned long long)s.originals, (unsigned long long)s.lost_originals,

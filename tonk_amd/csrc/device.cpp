@@ -12,21 +12,8 @@
 #include <stdlib.h>
 #include <string.h>
 
-extern "C" __global__ void tamd_exec24(tamd_segments, const uint8_t*, uint32_t, uint8_t*, const uint32_t*,
-                                        const uint8_t*, unsigned long long*);
-extern "C" __global__ void tamd_exec16(tamd_segments, const uint8_t*, uint32_t, uint8_t*, const uint32_t*,
-                                       const uint8_t*, unsigned long long*);
 typedef void (*ExecFn)(tamd_segments, const uint8_t*, uint32_t, uint8_t*, const uint32_t*, const uint8_t*,
                        unsigned long long*);
-extern "C" __global__ void tamd_gf_selftest(const uint32_t*, uint8_t*);
-extern "C" __global__ void tamd_timed_region();
-extern "C" __global__ void tamd_nop();
-extern "C" __global__ void tamd_gather_rows(const tamd::Device::GatherDesc*, uint32_t, const uint8_t*, uint8_t*);
-struct ScatterDescDev { uint32_t row, len, src, pad; };
-extern "C" __global__ void tamd_scatter_rows(const ScatterDescDev*, uint32_t, const uint8_t*, uint8_t*);
-struct HostCopyDev { uint64_t host; uint32_t unit, len; };
-extern "C" __global__ void tamd_host_copy(const HostCopyDev*, uint32_t, uint8_t*, uint32_t);
-extern "C" __global__ void tamd_copy_in(const uint4*, uint4*, uint32_t, const uint4*, uint4*, uint32_t);
 namespace {
 // Program uploads below this many bytes go through tamd_copy_in (a launch whose threads read the
 // pinned bytes) instead of the DMA engine, on devices that asked for it (set_small_uploads: few
@@ -46,14 +33,6 @@ void upload2(bool small_ok, void* d0, const void* h0, size_t b0, void* d1, const
     if (b1) hipMemcpyAsync(d1, h1, b1, hipMemcpyHostToDevice, st);
 }
 }  // namespace
-
-struct GenDescDev { uint32_t row, index, len, pad; unsigned long long seed; };
-struct DigestDescDev { uint32_t row, skip, len, pad; };
-extern "C" __global__ void tamd_gen_rows(const GenDescDev*, uint32_t, uint8_t*, uint32_t);
-extern "C" __global__ void tamd_digest_rows(const DigestDescDev*, uint32_t, const uint8_t*, unsigned long long*);
-struct VerifyDescDev { uint32_t row, len, mode, pad; };
-struct VerifyOutDev { unsigned long long hash; uint32_t len, ok; };
-extern "C" __global__ void tamd_verify_rows(const VerifyDescDev*, uint32_t, const uint8_t*, VerifyOutDev*);
 
 namespace tamd {
 
@@ -1184,7 +1163,7 @@ void Device::flush_uploads() {
     const size_t end = up_used_ + dbytes;
     HIPCHK(hipMemcpyAsync(up_dev_ + begin, up_host_ + begin, end - begin, hipMemcpyHostToDevice, st));
     // descriptor sources are offsets into up_dev_ (the same offsets as in up_host_)
-    HIPT(hipLaunchKernelGGL(tamd_scatter_rows, dim3(cnt), dim3(64), 0, st, (const ScatterDescDev*)(up_dev_ + up_used_), cnt,
+    HIPT(hipLaunchKernelGGL(tamd_scatter_rows, dim3(cnt), dim3(64), 0, st, (const ScatterDesc*)(up_dev_ + up_used_), cnt,
                        (const uint8_t*)up_dev_, arena_));
     HIPCHK(hipGetLastError());
     up_used_ = (end + 15) & ~(size_t)15;
@@ -1222,7 +1201,7 @@ void Device::scatter_upload(uint8_t* src, size_t bytes, const ScatterIn* d, uint
     // write-combined stores -- packets and the descriptors above -- must be out before the copy)
     _mm_sfence();
     HIPCHK(hipMemcpyAsync(sc_dev_, src, total, hipMemcpyDefault, st));
-    HIPT(hipLaunchKernelGGL(tamd_scatter_rows, dim3(n), dim3(64), 0, st, (const ScatterDescDev*)(sc_dev_ + at), n,
+    HIPT(hipLaunchKernelGGL(tamd_scatter_rows, dim3(n), dim3(64), 0, st, (const ScatterDesc*)(sc_dev_ + at), n,
                        (const uint8_t*)sc_dev_, arena_));
     HIPCHK(hipGetLastError());
     stats_.upload_bytes += total;
@@ -1293,7 +1272,7 @@ void Device::host_copy(const HostCopy* d, uint32_t n, bool to_host) {
     hc_next_ = pick + 1;
     HcBuf& b = hc_[pick];
     if (b.ev) HIPCHK(hipEventSynchronize((hipEvent_t)b.ev));  // (its previous launch has read it)
-    const size_t need = (size_t)n * sizeof(HostCopyDev);
+    const size_t need = (size_t)n * sizeof(HostCopyDesc);
     if (need > b.cap) {  // (pooled: hipHostFree would wait for the whole device)
         host_free(b.p);
         b.cap = need + need / 2 + 4096;
@@ -1304,7 +1283,7 @@ void Device::host_copy(const HostCopy* d, uint32_t n, bool to_host) {
             return;
         }
     }
-    HostCopyDev* hd = (HostCopyDev*)b.p;
+    HostCopyDesc* hd = (HostCopyDesc*)b.p;
     for (uint32_t k = 0; k < n; ++k) {
         if (((uintptr_t)d[k].host & 15u) || (d[k].arena_off & 63u) || d[k].arena_off / 64 > 0xffffffffull) {
             error_ = "host copy: unaligned host buffer or arena offset";
@@ -1315,7 +1294,7 @@ void Device::host_copy(const HostCopy* d, uint32_t n, bool to_host) {
         hd[k].unit = (uint32_t)(d[k].arena_off / 64);
         hd[k].len = d[k].len;
     }
-    HIPT(hipLaunchKernelGGL(tamd_host_copy, dim3(n), dim3(128), 0, st, (const HostCopyDev*)b.p, n, arena_, to_host ? 1u : 0u));
+    HIPT(hipLaunchKernelGGL(tamd_host_copy, dim3(n), dim3(128), 0, st, (const HostCopyDesc*)b.p, n, arena_, to_host ? 1u : 0u));
     HIPCHK(hipGetLastError());
     if (!b.ev) {
         hipEvent_t he;
@@ -1593,9 +1572,9 @@ void Device::generate_rows(const std::vector<GenDesc>& d, uint32_t row_cap) {
     flush_uploads();
     if (d.empty()) return;
     hipStream_t st = (hipStream_t)stream_;
-    GenDescDev* dd = nullptr;
-    HIPCHK(hipMalloc((void**)&dd, d.size() * sizeof(GenDescDev)));
-    HIPCHK(hipMemcpyAsync(dd, d.data(), d.size() * sizeof(GenDescDev), hipMemcpyHostToDevice, st));
+    GenDesc* dd = nullptr;
+    HIPCHK(hipMalloc((void**)&dd, d.size() * sizeof(GenDesc)));
+    HIPCHK(hipMemcpyAsync(dd, d.data(), d.size() * sizeof(GenDesc), hipMemcpyHostToDevice, st));
     const uint32_t n = (uint32_t)d.size();
     hipLaunchKernelGGL(tamd_gen_rows, dim3((n + 255) / 256), dim3(256), 0, st, dd, n, arena_, row_cap);
     HIPCHK(hipGetLastError());
@@ -1608,11 +1587,11 @@ void Device::digest_rows(const std::vector<DigestDesc>& d, std::vector<uint64_t>
     out.assign(d.size(), 0);
     if (d.empty()) return;
     hipStream_t st = (hipStream_t)stream_;
-    DigestDescDev* dd = nullptr;
+    DigestDesc* dd = nullptr;
     unsigned long long* dout = nullptr;
-    HIPCHK(hipMalloc((void**)&dd, d.size() * sizeof(DigestDescDev)));
+    HIPCHK(hipMalloc((void**)&dd, d.size() * sizeof(DigestDesc)));
     HIPCHK(hipMalloc((void**)&dout, d.size() * 8));
-    HIPCHK(hipMemcpyAsync(dd, d.data(), d.size() * sizeof(DigestDescDev), hipMemcpyHostToDevice, st));
+    HIPCHK(hipMemcpyAsync(dd, d.data(), d.size() * sizeof(DigestDesc), hipMemcpyHostToDevice, st));
     const uint32_t n = (uint32_t)d.size();
     hipLaunchKernelGGL(tamd_digest_rows, dim3((n + 255) / 256), dim3(256), 0, st, dd, n, arena_, dout);
     HIPCHK(hipGetLastError());
@@ -1642,7 +1621,7 @@ void Device::verify_next(const std::vector<VerifyDesc>& d) {
 void Device::run_verify(int batch) {
     const VerifyBatch& b = vbatches_[batch];
     hipLaunchKernelGGL(tamd_verify_rows, dim3((b.count + 63) / 64), dim3(64), 0, (hipStream_t)stream_,
-                       (const VerifyDescDev*)b.dev_desc, b.count, (const uint8_t*)arena_, (VerifyOutDev*)b.dev_out);
+                       b.dev_desc, b.count, (const uint8_t*)arena_, b.dev_out);
     HIPCHK(hipGetLastError());
 }
 

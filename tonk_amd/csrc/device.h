@@ -3,6 +3,7 @@
 #pragma once
 
 #include "engine.h"
+#include "kernel_abi.h"
 
 #include <stdint.h>
 #include <atomic>
@@ -104,9 +105,13 @@ public:
     void begin(Context* const* ctxs, size_t n, bool closed = false);
     void fill(size_t i);
     uint64_t launch();
-    // (verification descriptors, see verify_next below)
-    struct VerifyDesc { uint32_t row, len, mode, pad; };
-    struct VerifyOut { uint64_t hash; uint32_t len, ok; };
+    // the helper kernels' records (kernel_abi.h)
+    typedef ::GenDesc GenDesc;
+    typedef ::GatherDesc GatherDesc;
+    typedef ::ScatterDesc ScatterDesc;
+    typedef ::DigestDesc DigestDesc;
+    typedef ::VerifyDesc VerifyDesc;  // (see verify_next below)
+    typedef ::VerifyOut VerifyOut;
 
     // Parallel assembly without a layout pass (the session's free-running schedule).  A program
     // is opened (its staging slot: the slot's previous program must have completed), then any
@@ -192,9 +197,7 @@ public:
     static void bar_free(void* p);
 
     // Bench helpers (kernels.hip).
-    struct GenDesc { uint32_t row, index, len, pad; uint64_t seed; };
     void generate_rows(const std::vector<GenDesc>& d, uint32_t row_cap);
-    struct DigestDesc { uint32_t row, skip, len, pad; };
     void digest_rows(const std::vector<DigestDesc>& d, std::vector<uint64_t>& out);
 
     // Output verification of the schedule as it runs (the session's record mode): the rows of
@@ -214,7 +217,6 @@ public:
     // the copies enqueued so far.  d2h_gather() packs rows (after everything enqueued on the
     // compute stream) into a device buffer and copies it to `pinned_dst` on a third stream;
     // h2d_after_d2h() then copies `n` bytes of it back (the received-recovery direction).
-    struct GatherDesc { uint32_t row, len, out; };
     bool enable_staging();
     void h2d(uint64_t arena_offset, const void* pinned_src, size_t n);
     void h2d_fence();
@@ -346,7 +348,6 @@ private:
     bool ticket_is_empty_ = false;
     void mark(uint64_t ticket);
     // upload staging: packets at [up_flushed_, up_used_) of up_host_ are not enqueued yet
-    struct ScatterDesc { uint32_t row, len, src, pad; };
     uint8_t* up_host_ = nullptr;
     uint8_t* up_dev_ = nullptr;
     uint8_t* sc_dev_ = nullptr;  // scatter_upload landing area (of the current stream)

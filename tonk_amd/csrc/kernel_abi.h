@@ -1,0 +1,51 @@
+// kernel_abi.h -- the records the helper kernels of kernels.hip read and write, and the
+// prototypes of every kernel the host launches (device.cpp, server.cpp): one definition for both
+// sides.  The records are plain C; the prototypes need a HIP translation unit.
+#pragma once
+#include <stdint.h>
+
+#include "program.h"
+#include "serve.h"
+
+/* tamd_gen_rows: row offset (64-B units), packet index, payload length, row capacity, seed_data */
+typedef struct GenDesc { uint32_t row, index, len, cap; uint64_t seed; } GenDesc;
+/* tamd_gather_rows: arena row, bytes, output offset */
+typedef struct GatherDesc { uint32_t row, len, out; } GatherDesc;
+/* tamd_scatter_rows: arena row, bytes, offset in the staging buffer */
+typedef struct ScatterDesc { uint32_t row, len, src, pad; } ScatterDesc;
+/* tamd_host_copy: pinned host address, arena row, bytes */
+typedef struct HostCopyDesc { uint64_t host; uint32_t unit, len; } HostCopyDesc;
+/* tamd_digest_rows: FNV-1a 64 over `len` bytes starting `skip` bytes into the row */
+typedef struct DigestDesc { uint32_t row, skip, len, pad; } DigestDesc;
+/* tamd_verify_rows: mode 0 a recovery packet of `len` bytes, 1 a recovered original */
+typedef struct VerifyDesc { uint32_t row, len, mode, pad; } VerifyDesc;
+typedef struct VerifyOut { uint64_t hash; uint32_t len, ok; } VerifyOut;
+
+static_assert(sizeof(GenDesc) == 24, "GenDesc");
+static_assert(sizeof(GatherDesc) == 12, "GatherDesc");
+static_assert(sizeof(ScatterDesc) == 16, "ScatterDesc");
+static_assert(sizeof(HostCopyDesc) == 16, "HostCopyDesc");
+static_assert(sizeof(DigestDesc) == 16, "DigestDesc");
+static_assert(sizeof(VerifyDesc) == 16, "VerifyDesc");
+static_assert(sizeof(VerifyOut) == 16, "VerifyOut");
+
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+extern "C" {
+__global__ void tamd_exec16(tamd_segments, const uint8_t*, uint32_t, uint8_t*, const uint32_t*, const uint8_t*,
+                            unsigned long long*);
+__global__ void tamd_exec24(tamd_segments, const uint8_t*, uint32_t, uint8_t*, const uint32_t*, const uint8_t*,
+                            unsigned long long*);
+__global__ void tamd_serve(const tamd_serve_args);
+__global__ void tamd_gf_selftest(const uint32_t*, uint8_t*);
+__global__ void tamd_gen_rows(const GenDesc*, uint32_t, uint8_t*, uint32_t);
+__global__ void tamd_gather_rows(const GatherDesc*, uint32_t, const uint8_t*, uint8_t*);
+__global__ void tamd_scatter_rows(const ScatterDesc*, uint32_t, const uint8_t*, uint8_t*);
+__global__ void tamd_host_copy(const HostCopyDesc*, uint32_t, uint8_t*, uint32_t);
+__global__ void tamd_copy_in(const uint4*, uint4*, uint32_t, const uint4*, uint4*, uint32_t);
+__global__ void tamd_digest_rows(const DigestDesc*, uint32_t, const uint8_t*, unsigned long long*);
+__global__ void tamd_verify_rows(const VerifyDesc*, uint32_t, const uint8_t*, VerifyOut*);
+__global__ void tamd_timed_region();
+__global__ void tamd_nop();
+}
+#endif

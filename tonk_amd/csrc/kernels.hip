@@ -10,8 +10,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "program.h"
-#include "serve.h"
+#include "kernel_abi.h"
 
 #define TAMD_WAVES_PER_WG 4
 
@@ -1319,8 +1318,6 @@ struct DevPcg {
 // Synthetic input rows (tonk_amd/csrc/workload.h payload_bytes): for each descriptor
 // {row offset (64-B units), packet index, payload length, row capacity, seed_data}, write
 // varint(len) || PCG bytes and zero-fill to the capacity.  One thread per packet (setup only).
-struct GenDesc { uint32_t row, index, len, cap; u64 seed; };
-
 extern "C" __global__ void tamd_gen_rows(const GenDesc* __restrict__ d, uint32_t n, uint8_t* __restrict__ arena,
                                           uint32_t row_cap) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1353,8 +1350,6 @@ extern "C" __global__ void tamd_gen_rows(const GenDesc* __restrict__ d, uint32_t
 
 // Host staging (device.cpp d2h_gather): pack rows {arena row, bytes, output offset} into one
 // buffer for a single D2H copy.  One workgroup per row, 16-byte stores where aligned.
-struct GatherDesc { uint32_t row, len, out; };
-
 extern "C" __global__ void tamd_gather_rows(const GatherDesc* __restrict__ d, uint32_t n,
                                             const uint8_t* __restrict__ arena, uint8_t* __restrict__ out) {
     const GatherDesc g = d[blockIdx.x];
@@ -1367,8 +1362,6 @@ extern "C" __global__ void tamd_gather_rows(const GatherDesc* __restrict__ d, ui
 
 // Coalesced uploads of the siamese.h C ABI (Device::upload): packets staged back to back in one
 // buffer (16-B aligned), one workgroup per packet copies it into its arena row (64-B aligned).
-struct ScatterDesc { uint32_t row, len, src, pad; };
-
 extern "C" __global__ void tamd_scatter_rows(const ScatterDesc* __restrict__ d, uint32_t n,
                                              const uint8_t* __restrict__ in, uint8_t* __restrict__ arena) {
     const ScatterDesc g = d[blockIdx.x];
@@ -1382,8 +1375,6 @@ extern "C" __global__ void tamd_scatter_rows(const ScatterDesc* __restrict__ d, 
 // Zero-copy transfers between pinned host memory and the arena (Device::host_copy): one
 // workgroup per packet reads (to_host = 0) or writes (1) the host bytes over the link directly.
 // Host addresses are 16-B aligned, arena rows 64-B aligned.
-struct HostCopyDesc { u64 host; uint32_t unit, len; };
-
 extern "C" __global__ void __launch_bounds__(128)
 tamd_host_copy(const HostCopyDesc* __restrict__ d, uint32_t n, uint8_t* __restrict__ arena, uint32_t to_host) {
     const HostCopyDesc c = d[blockIdx.x];
@@ -1412,8 +1403,6 @@ tamd_copy_in(const uint4* __restrict__ s0, uint4* __restrict__ d0, uint32_t n0, 
 
 // Digest of rows (FNV-1a 64 over `len` bytes starting `skip` bytes into the row): one thread
 // per row, for output verification after a timed run (not on the timed path).
-struct DigestDesc { uint32_t row, skip, len, pad; };
-
 extern "C" __global__ void tamd_digest_rows(const DigestDesc* __restrict__ d, uint32_t n,
                                              const uint8_t* __restrict__ arena, u64* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1430,9 +1419,6 @@ extern "C" __global__ void tamd_digest_rows(const DigestDesc* __restrict__ d, ui
 // (a recovery packet, footer included); mode 1: a recovered original -- parse its length
 // prefix (serial.h get_length_header, `len` bytes available) and hash the payload it announces.
 // One thread per row; verification only, never in a timed region.
-struct VerifyDesc { uint32_t row, len, mode, pad; };
-struct VerifyOut { u64 hash; uint32_t len, ok; };
-
 extern "C" __global__ void tamd_verify_rows(const VerifyDesc* __restrict__ d, uint32_t n,
                                             const uint8_t* __restrict__ arena, VerifyOut* __restrict__ out) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;

@@ -14,8 +14,6 @@
 #include <unistd.h>
 #include <time.h>
 
-extern "C" __global__ void tamd_serve(const tamd_serve_args);
-
 namespace tamd {
 
 namespace {

@@ -7,9 +7,8 @@
 // executes; rows freed during a step are reused only once that step's program has completed.
 #include "../../include/tonk_amd.h"
 
-#include "decoder.h"
 #include "device.h"
-#include "workload.h"
+#include "resident_backend.h"
 #include "transcript.h"
 
 #include <hip/hip_runtime.h>
@@ -174,179 +173,69 @@ std::vector<int> idle_cpus(const std::vector<int>& share, size_t want) {
     return pick_idle(share, d, want);
 }
 
-struct Stream;
-
-// Transcript in the oracle's format (record mode).  The digests of device rows are computed on
-// the device (Device::verify_next) right after the launch that completes their program, and
-// filled into the lines at the end of the run.
-struct SessTranscript {
-    bool on = false;
-    std::vector<std::string> lines;
-    // rows whose digest goes into line `pos`; `v` = index of the digest among the session's
-    // verification results (assigned when the rows are registered after their pass)
-    struct PendEnc { RowId row; uint32_t total; RecoveryMeta meta; size_t pos; uint64_t v; };
-    struct PendDec { RowId row; uint32_t upper; size_t pos; uint64_t v; };
-    std::vector<PendEnc> pend_enc;
-    std::vector<PendDec> pend_dec;
-    size_t reg_enc = 0, reg_dec = 0;  // entries [0, reg_*) are registered
-};
-
-struct Stream {
+// A session's stream: the resident backend plus what only a session has -- the rows that leave
+// or arrive through PCIe (stage_host) and the record-mode transcript in the oracle's format.
+// The digests of device rows are computed on the device (Device::verify_next) right after the
+// launch that completes their program, and filled into the lines at the end of the run; a
+// pending entry's tag is the index of its digest among the session's verification results
+// (assigned when the rows are registered after their pass).
+struct Stream : ResidentBackend {
     wl::Params p;
-    Context* ctx = nullptr;
-    std::unique_ptr<Encoder> enc;
-    std::unique_ptr<Decoder> dec;
-    std::vector<RowId> enc_rows, dec_rows;
-    uint32_t pool = 0;        // input rows per side (original i reads row i mod pool)
-    bool pool_affine = false; // each side's pool rows are consecutive handles at one arena stride:
-    uint32_t pool_off[2] = {0, 0}, pool_stride = 0;  // row i mod pool at pool_off[side] + (i mod pool) * stride
-    std::vector<uint32_t> framed;
-    std::vector<uint8_t> dec_row_used;
-    SessTranscript tr;
-    uint64_t alg_bytes = 0, payload_bytes = 0;
+    bool record = false;
+    wl::DeferredTranscript tr;
+    size_t reg_enc = 0, reg_dec = 0;  // tr.pend_* entries [0, reg_*) are registered
     // stage_host: rows this step produced that leave through PCIe (recovery packets, recovered
     // originals) and the recovery bytes the decoder received (which arrived through PCIe)
     uint32_t stage = 0;  // stage_host mask: 1 sender side staged, 2 receiver side
     std::vector<std::pair<RowId, uint32_t>> out_rows;
     uint64_t recv_bytes = 0;
 
-    // ---- workload backend ----
-    struct RecRef { RecoveryOut out; };
-    struct DecRef {};
-
-    int enc_add(uint32_t index, uint32_t len, uint32_t* col) {
-        const uint32_t hb = length_header_bytes(len);
-        // input rows are generated once in HBM and borrowed by the codecs (never freed)
-        const Result r = enc->add(enc_rows[index], hb + len, hb, len, nullptr, col, true);
-        if (r == kSuccess) {
-            alg_bytes += hb + len;
-            payload_bytes += len;
-        }
-        return r;
-    }
-    // Input rows were allocated back to back per side (generate), so a run that does not wrap
-    // the input pool is consecutive handles at one stride: the codecs get its layout instead of
-    // checking and looking it up (the row table is cold).
-    uint64_t layout(int side, uint32_t index, uint32_t k) const {
-        if (!pool_affine || index % pool + k > pool) return 0;
-        return (uint64_t)(pool_off[side] + (index % pool) * pool_stride) << 32 | pool_stride;
-    }
-    bool enc_add_run(uint32_t index, uint32_t k, uint32_t len, uint32_t* col0) {
-        const uint32_t hb = length_header_bytes(len);
-        if (!enc->add_run(&enc_rows[index], k, hb + len, hb, len, true, col0, layout(0, index, k))) return false;
-        alg_bytes += (uint64_t)(hb + len) * k;
-        payload_bytes += (uint64_t)len * k;
-        return true;
-    }
-    bool dec_add_run(uint32_t col0, uint32_t index, uint32_t k, uint32_t len) {
-        const uint32_t hb = length_header_bytes(len);
-        if (!dec->add_run_inorder(col0, &dec_rows[index], k, hb + len, hb, len, true, layout(1, index, k))) return false;
-        alg_bytes += (uint64_t)(hb + len) * k;
-        return true;
-    }
     int enc_encode(RecRef& r) {
-        const Result rc = enc->encode(r.out);
-        if (rc == kSuccess) {
-            alg_bytes += r.out.total();
-            if (stage & 1u) out_rows.push_back(std::make_pair(r.out.row, r.out.total()));
-        }
+        const int rc = ResidentBackend::enc_encode(r);
+        if (rc == 0 && (stage & 1u)) out_rows.push_back(std::make_pair(r.out.row, r.out.total()));
         return rc;
     }
-    int enc_ack(const uint8_t* buf, uint32_t n, uint32_t* next) { return enc->acknowledge(buf, n, next); }
-    int enc_is_ready() { return enc->remaining_slots() <= 2 ? (int)kMaxPacketsReached : 0; }
-    int dec_add_original(uint32_t col, uint32_t index, uint32_t len) {
-        const uint32_t hb = length_header_bytes(len);
-        bool took = false;
-        const Result r = dec->add_original(col, dec_rows[index], hb + len, hb, len, nullptr, &took, true);
-        alg_bytes += hb + len;
-        return r;
-    }
-    void recovery_lost(const RecRef& r) { ctx->rows.free_deferred(r.out.row); }
     int dec_add_recovery(const RecRef& r) {
-        uint8_t tail[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const uint32_t tl = r.out.total() < 8 ? r.out.total() : 8;
-        memcpy(tail + tl - r.out.footer_len, r.out.footer, r.out.footer_len);
-        bool took = false;
-        const Result rc = dec->add_recovery(r.out.row, r.out.total(), tail, nullptr, &took);
-        if (!took) ctx->rows.free_deferred(r.out.row);
-        alg_bytes += r.out.total();
         if (stage & 2u) recv_bytes += r.out.total();
-        return rc;
+        return ResidentBackend::dec_add_recovery(r);
     }
-    int dec_is_ready() { return dec->is_ready(); }
-    std::vector<RecoveredPacket*> got_;
-    int dec_decode(std::vector<uint32_t>& nums, DecRef&) {
-        got_.clear();
-        const Result rc = dec->decode(got_);
-        if (rc == kSuccess) {
+    int dec_decode(std::vector<uint32_t>& nums, DecRef& d) {
+        const int rc = ResidentBackend::dec_decode(nums, d);
+        if ((stage & 2u) || record)
             for (RecoveredPacket* rp : got_) {
-                nums.push_back(rp->packet_num);
-                alg_bytes += rp->framed_upper;
                 if (stage & 2u) out_rows.push_back(std::make_pair(rp->row, rp->framed_upper));
-                if (tr.on) tr.pend_dec.push_back(SessTranscript::PendDec{rp->row, rp->framed_upper, tr.lines.size(), 0});
+                if (record) tr.recovered(rp->row, rp->framed_upper);
             }
-        }
-        return rc;
-    }
-    int dec_ack(uint8_t* buf, uint32_t limit, uint32_t* used) { return dec->ack(buf, limit, used); }
-    void stats(uint64_t e[9], uint64_t d[11]) { enc->stats(e, 9); dec->stats(d, 11); }
-    uint64_t vclock = 0;
-    void set_time(uint64_t ms) {
-        if (!vclock) enc->set_clock(&vclock);
-        vclock = ms;
-    }
-    int enc_retransmit(uint32_t* num, uint32_t* bytes, const uint8_t** data) {
-        StoredOriginal ov;
-        const StoredOriginal* o = &ov;
-        const Result rc = enc->retransmit(&ov);
-        if (rc == kSuccess) {
-            *num = o->column;
-            *bytes = o->bytes - o->header_bytes;
-            *data = nullptr;  // the payload lives in HBM; the runner regenerates it for the digest
-        }
         return rc;
     }
 
     // ---- transcript ----
     void on_encode(int rc, const RecRef& r) {
-        if (!tr.on) return;
-        if (rc != 0) { tr.lines.push_back("E " + std::to_string(rc)); return; }
-        tr.pend_enc.push_back(SessTranscript::PendEnc{r.out.row, r.out.total(), r.out.meta, tr.lines.size(), 0});
-        tr.lines.push_back("E ?");
+        if (record)
+            tr.encode(rc, r.out.row, r.out.total(), r.out.meta.Row, r.out.meta.ColumnStart, r.out.meta.SumCount,
+                      r.out.meta.LDPCCount);
     }
-    void on_decode(int rc, const std::vector<uint32_t>& nums, const DecRef&) {
-        if (!tr.on) return;
-        std::string ln = "D " + std::to_string(rc) + " " + std::to_string(nums.size());
-        for (uint32_t n : nums) ln += " " + std::to_string(n) + "#";
-        // pend_dec entries were pushed with pos = lines.size() before this line is appended
-        tr.lines.push_back(ln);
-    }
+    void on_decode(int rc, const std::vector<uint32_t>& nums, const DecRef&) { if (record) tr.decode(rc, nums); }
     void on_ack(int rd, const uint8_t* buf, uint32_t used, int re, uint32_t next) {
-        if (!tr.on) return;
-        char b[128];
-        snprintf(b, sizeof(b), "K %d %u %016llx %d %u", rd, used, (unsigned long long)wl::fnv1a(buf, used), re, next);
-        tr.lines.push_back(b);
+        if (record) tr.ack(rd, buf, used, re, next);
     }
-    void on_event(char kind, int rc, uint32_t a, uint32_t b) {
-        if (!tr.on || rc == 0) return;
-        char t[64];
-        snprintf(t, sizeof(t), "%c %d %u %u", kind, rc, a, b);
-        tr.lines.push_back(t);
-    }
-    void on_retransmit(int rc, uint32_t num, uint32_t bytes, uint64_t h) {
-        if (!tr.on) return;
-        wl::TextSink t;
-        wl::fmt_retransmit(t, rc, num, bytes, h);
-        t.text.pop_back();
-        tr.lines.push_back(t.text);
-    }
-    void on_stats(const uint64_t e[9], const uint64_t d[11]) {
-        if (!tr.on) return;
-        std::string s = "S";
-        for (int i = 0; i < 8; ++i) s += " " + std::to_string(e[i]);
-        s += " |";
-        for (int i = 0; i < 10; ++i) s += " " + std::to_string(d[i]);
-        tr.lines.push_back(s);
+    void on_event(char kind, int rc, uint32_t a, uint32_t b) { if (record) tr.event(kind, rc, a, b); }
+    void on_retransmit(int rc, uint32_t num, uint32_t bytes, uint64_t h) { if (record) tr.retransmit(rc, num, bytes, h); }
+    void on_stats(const uint64_t e[9], const uint64_t d[11]) { if (record) tr.stats(e, d); }
+    // The rows of the entries not registered yet, as verification descriptors in the order
+    // their digests come back; next_tag() numbers them.
+    template <class NextTag>
+    void register_verify(std::vector<Device::VerifyDesc>& d, NextTag next_tag) {
+        for (; reg_enc < tr.pend_enc.size(); ++reg_enc) {
+            wl::DeferredTranscript::Enc& e = tr.pend_enc[reg_enc];
+            e.tag = next_tag();
+            d.push_back(Device::VerifyDesc{(uint32_t)ctx->rows.offset(e.row), e.total, 0, 0});
+        }
+        for (; reg_dec < tr.pend_dec.size(); ++reg_dec) {
+            wl::DeferredTranscript::Dec& e = tr.pend_dec[reg_dec];
+            e.tag = next_tag();
+            d.push_back(Device::VerifyDesc{(uint32_t)ctx->rows.offset(e.row), e.upper, 1, 0});
+        }
     }
 
     std::unique_ptr<wl::Runner<Stream, Stream>> runner;
@@ -704,21 +593,11 @@ struct Session {
         Device::Part& part = st.parts[k % kFrRing];
         dev.add_part(P.handle, c.pb, part);
         part.verify.clear();
-        if (st.tr.on) {
+        if (st.record) {
             // record mode: the digests of this step's rows, taken once program k completes;
             // an entry's index is (program, position in this stream's part)
-            SessTranscript& t = st.tr;
             uint64_t local = 0;
-            for (size_t e = t.reg_enc; e < t.pend_enc.size(); ++e) {
-                t.pend_enc[e].v = ((uint64_t)k << 32) | local++;
-                part.verify.push_back(Device::VerifyDesc{(uint32_t)c.rows.offset(t.pend_enc[e].row), t.pend_enc[e].total, 0, 0});
-            }
-            for (size_t e = t.reg_dec; e < t.pend_dec.size(); ++e) {
-                t.pend_dec[e].v = ((uint64_t)k << 32) | local++;
-                part.verify.push_back(Device::VerifyDesc{(uint32_t)c.rows.offset(t.pend_dec[e].row), t.pend_dec[e].upper, 1, 0});
-            }
-            t.reg_enc = t.pend_enc.size();
-            t.reg_dec = t.pend_dec.size();
+            st.register_verify(part.verify, [&] { return ((uint64_t)k << 32) | local++; });
         }
         c.finish_flush(false);
         busy_ms[ti] += std::chrono::duration<double, std::milli>(clk::now() - w0).count();
@@ -1067,21 +946,7 @@ struct Session {
     uint64_t verify_count = 0, verify_base = 0;
     void register_verify() {
         std::vector<Device::VerifyDesc> d;
-        for (auto& sp : streams) {
-            SessTranscript& t = sp->tr;
-            for (size_t k = t.reg_enc; k < t.pend_enc.size(); ++k) {
-                auto& e = t.pend_enc[k];
-                e.v = verify_count++;
-                d.push_back(Device::VerifyDesc{(uint32_t)sp->ctx->rows.offset(e.row), e.total, 0, 0});
-            }
-            for (size_t k = t.reg_dec; k < t.pend_dec.size(); ++k) {
-                auto& e = t.pend_dec[k];
-                e.v = verify_count++;
-                d.push_back(Device::VerifyDesc{(uint32_t)sp->ctx->rows.offset(e.row), e.upper, 1, 0});
-            }
-            t.reg_enc = t.pend_enc.size();
-            t.reg_dec = t.pend_dec.size();
-        }
+        for (auto& sp : streams) sp->register_verify(d, [this] { return verify_count++; });
         dev.verify_next(d);
     }
 
@@ -1102,27 +967,14 @@ struct Session {
         };
         for (auto& sp : streams) {
             Stream& s = *sp;
-            char line[256];
-            for (auto& e : s.tr.pend_enc) {
-                const Device::VerifyOut& o = get(e.v);
-                snprintf(line, sizeof(line), "E 0 %u %u %u %u %u %016llx", e.total, e.meta.Row, e.meta.ColumnStart,
-                         e.meta.SumCount, e.meta.LDPCCount, (unsigned long long)o.hash);
-                s.tr.lines[e.pos] = line;
+            for (size_t k = 0; k < s.tr.pend_enc.size(); ++k) s.tr.resolve_enc(k, get(s.tr.pend_enc[k].tag).hash);
+            for (size_t k = 0; k < s.tr.pend_dec.size(); ++k) {
+                const Device::VerifyOut& o = get(s.tr.pend_dec[k].tag);
+                if (o.ok) s.tr.resolve_dec(k, o.len, o.hash);
+                else error = "recovered row with a corrupt length header";
             }
-            for (auto& d : s.tr.pend_dec) {
-                const Device::VerifyOut& o = get(d.v);
-                if (!o.ok) {
-                    error = "recovered row with a corrupt length header";
-                    continue;
-                }
-                std::string& ln = s.tr.lines[d.pos];
-                snprintf(line, sizeof(line), ":%u:%016llx", o.len, (unsigned long long)o.hash);
-                const size_t at = ln.find('#');
-                if (at != std::string::npos) ln.replace(at, 1, line);
-            }
-            s.tr.pend_enc.clear();
-            s.tr.pend_dec.clear();
-            s.tr.reg_enc = s.tr.reg_dec = 0;
+            s.tr.resolved();
+            s.reg_enc = s.reg_dec = 0;
             ++si;
         }
         verify_base = verify_count;
@@ -1238,7 +1090,7 @@ void* tamd_session_create(const tamd_session_params* p, char* err, size_t err_le
         st->enc.reset(new Encoder(ctx.get(), raw->row_cap));
         st->enc->set_clock(&st->clock);
         st->dec.reset(new Decoder(ctx.get(), raw->row_cap));
-        st->tr.on = p->record != 0;
+        st->record = p->record != 0;
         st->runner.reset(new wl::Runner<Stream, Stream>(st->p, *st, *st));
         raw->streams[i] = std::move(st);
         raw->ctxs[i] = std::move(ctx);
@@ -1256,43 +1108,24 @@ int tamd_session_generate(void* sp) {
         std::vector<Device::GenDesc>& d = per[si];
         const uint32_t n = st.p.n_originals;
         st.runner->pregenerate();  // the stream's loss draws (scenario generation, untimed)
-        st.enc_rows.assign(n, kNoRow);
-        st.dec_rows.assign(n, kNoRow);
         // (an input pool: rows for the first `pool` originals; original i reads row i mod pool)
         // (equal payload lengths only: a pooled row's length header must be original i's)
         const uint32_t pool = s->prm.input_pool && s->prm.input_pool < n && !s->prm.record &&
                                       !s->prm.stage_host && st.p.payload_min == st.p.payload_max
                                   ? s->prm.input_pool : n;
+        if (!st.alloc_inputs(n, pool, s->row_cap)) { full = true; return; }
         d.reserve(2 * (size_t)pool);
-        // Each side's inputs are an array of equal slots (row_cap bytes) in packet order, so runs of
-        // a window's packets sit at a fixed stride (one ACCR instruction per run).
-        for (int side = 0; side < 2; ++side) {
+        for (int side = 0; side < 2; ++side)
             for (uint32_t i = 0; i < pool; ++i) {
-                const uint32_t len = wl::payload_length(st.p, i);
-                const RowId r = st.ctx->alloc(s->row_cap);
-                if (r == kNoRow) { full = true; return; }
-                (side ? st.dec_rows : st.enc_rows)[i] = r;
+                const RowId r = (side ? st.dec_rows : st.enc_rows)[i];
                 Device::GenDesc g;
                 g.row = st.ctx->rows.offset(r);
                 g.index = i;
-                g.len = len;
-                g.pad = st.ctx->rows.cap_bytes(r);
+                g.len = wl::payload_length(st.p, i);
+                g.cap = st.ctx->rows.cap_bytes(r);
                 g.seed = st.p.seed_data;
                 d.push_back(g);
             }
-            std::vector<RowId>& rows = side ? st.dec_rows : st.enc_rows;
-            for (uint32_t i = pool; i < n; ++i) rows[i] = rows[i - pool];
-        }
-        st.pool = pool;
-        st.pool_affine = pool >= 2;
-        for (int side = 0; side < 2 && st.pool_affine; ++side) {
-            const std::vector<RowId>& rows = side ? st.dec_rows : st.enc_rows;
-            const uint32_t o0 = st.ctx->rows.offset(rows[0]), stride = st.ctx->rows.offset(rows[1]) - o0;
-            st.pool_affine = consecutive_handles(rows.data(), pool) && stride > 0 &&
-                             st.ctx->rows.affine(rows[0], pool, stride) && (!side || stride == st.pool_stride);
-            st.pool_off[side] = o0;
-            st.pool_stride = stride;
-        }
     });
     if (full) { s->error = "arena too small for the session inputs"; return -1; }
     std::vector<Device::GenDesc> d;

@@ -84,7 +84,8 @@ inline uint32_t index_of_column(uint32_t col, uint32_t top) {
 static const uint32_t kRtxPerTick = 4;
 static const uint64_t kVirtualClockStart = 1000;  // ms (send times are never 0)
 
-// key=value workload arguments shared by every driver (golden_gen, cp_harness, cp_bench).
+// key=value workload arguments shared by every driver (golden_gen, cp_harness, and cp_bench and
+// prog_digest through tests/native/resident_streams.h).
 // Returns false for an unknown key.
 inline bool parse_param(Params& p, const std::string& k, unsigned long long v) {
     if (k == "stream") p.stream_id = (uint32_t)v;
