@@ -636,6 +636,8 @@ static void add_cases(std::vector<Spec>& out) {
             ProgramBuilder& pb = c.pb();
             for (uint32_t v = 0; v < 6; ++v) {
                 const uint32_t L = kL[(6 * ci + v + 1) % (kNL - 1)], st = units_of(L) + (v & 1u);
+                // the odd variants: a column step other than 1 (the format allows any)
+                const uint32_t cstep = v == 3 ? 3 : v & 1u ? 8 : 1;
                 const uint32_t K = TAMD_R_CAUCHY, X = TAMD_R_CONST;
                 auto P = [&]() { return c.rng.u(192); };
                 uint32_t t[3] = {0, 0, 0};
@@ -648,7 +650,7 @@ static void add_cases(std::vector<Spec>& out) {
                 default: t[0] = tword(X, 0, 0, (C + 1) / 2), t[1] = tword(K, P(), C / 2, C); break;
                 }
                 pb.begin_op();
-                pb.op_accr_multi(c.region(C, st, L), st, C, L, c.rng.u(1u << 22), 1, t);
+                pb.op_accr_multi(c.region(C, st, L), st, C, L, c.rng.u(1u << 22), cstep, t);
                 for (uint32_t a = 0; a < 3; ++a) pb.op_store(c.alloc(L + a + 1), L, a, c.footer(), a + 1);
                 pb.end_op();
             }
@@ -1147,8 +1149,8 @@ static void print_reach(Case& c, const std::vector<Prog>& progs, uint64_t dig) {
                 }
                 adj += words;
                 targets += nt;
-                snprintf(buf, sizeof buf, "%s{\"mode\":%u,\"p\":%u,\"scale\":%u,\"count\":%u,\"len\":%u,\"stride\":%u,\"targets\":%u,\"adj\":%u}",
-                         runs.size() > 1 ? "," : "", r.mode, r.p, r.scale, r.count, r.len, r.stride, nt, words);
+                snprintf(buf, sizeof buf, "%s{\"mode\":%u,\"p\":%u,\"scale\":%u,\"count\":%u,\"len\":%u,\"stride\":%u,\"cstep\":%u,\"targets\":%u,\"adj\":%u}",
+                         runs.size() > 1 ? "," : "", r.mode, r.p, r.scale, r.count, r.len, r.stride, r.cstep, nt, words);
                 runs += buf;
                 k += r.words;
             }

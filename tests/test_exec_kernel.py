@@ -163,6 +163,9 @@ def test_reach_multi():
     m = runs_of(g, MULTI)
     assert sorted({r["count"] for r in m}) == C_ALL
     assert {r["targets"] for r in m} == {1, 2, 3}
+    # column steps other than 1 (the executor derives a row's column from col0, the step and the row's index)
+    for step in (3, 8):
+        assert sorted({r["count"] for r in m if r["cstep"] == step}) == C_ALL
     assert all(o["pure"] == 0 for c in g for o in c["ops"])
 
 

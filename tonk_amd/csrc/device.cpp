@@ -234,7 +234,8 @@ bool Device::init(int device, uint64_t arena_bytes) {
         per_cu < 1)
         per_cu = 1;
     // The occupancy API ignores the SGPR limit (MI355X_MICROARCH.md, Correctness boundaries): at
-    // tamd_exec16's ~106 SGPRs a SIMD holds floor(800 / 128) = 6 waves, i.e. 6 workgroups per CU.
+    // the 106 SGPRs of either executor kernel a SIMD holds floor(800 / 128) = 6 waves, i.e. 6
+    // workgroups per CU.
     if (per_cu > 6) per_cu = 6;
     max_grid_ = (uint32_t)per_cu * (uint32_t)prop.multiProcessorCount;
     HIPCHK(hipSetDevice(device));
@@ -878,9 +879,6 @@ void Device::launch_step(Inflight* fresh, unsigned long long* stamps) {
     if (!cnt) return;
     // Segment order = the order waves claim items in: programs oldest first (deepest level
     // first, the new program's level 1 last).
-    // Items class by class across the segments: the launch's long items (every level's class 0)
-    // are taken first (program.h: the host never sends flags = 0)
-    sg.flags = 1u;
     hipStream_t st = (hipStream_t)stream_;
     // Class-0 ops are shared by a workgroup only in launches too small to fill the chip twice
     // over with single-wave items; in the big ones they run as ordinary (first) items.  Only the

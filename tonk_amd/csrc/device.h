@@ -247,7 +247,7 @@ private:
     uint8_t* d_zero_ = nullptr;
     bool small_uploads_ = false;
     uint32_t max_grid_ = 256;
-    const void* exec_kernel_ = nullptr;  // tamd_exec16
+    const void* exec_kernel_ = nullptr;  // tamd_exec24, or tamd_exec16 under TONK_AMD_SLICE=1024
     // host staging
     void* h2d_stream_ = nullptr;
     void* d2h_stream_ = nullptr;

@@ -1,8 +1,10 @@
 // kernels.hip -- CDNA4 (gfx950) kernels of the Siamese engine.
 //
-// tamd_exec16 runs one level of a device program (program.h).  A work item is one op over a
-// 1024-byte slice of its rows: one 64-lane wave owns 16 bytes per lane of the op's three
-// accumulators and walks the op's instruction list (wave-uniform, scalar loads).  GF(2^8)
+// The executor (tamd_exec24, the default, and tamd_exec16: exec_level below) runs one level of a
+// device program (program.h).  A work item is one op over a slice of its rows, 1536 or 1024 bytes:
+// one 64-lane wave owns 16 (+ 8) bytes per lane of the op's three accumulators and walks the op's
+// instruction list (wave-uniform, scalar loads).  tamd_serve runs the same items from its own
+// persistent grid.  GF(2^8)
 // multiplication by a wave-uniform coefficient uses three 8-entry product tables per
 // coefficient staged in LDS and v_perm_b32 byte lookups (x*c = T0[x&7] ^ T1[(x>>3)&7] ^
 // T2[x>>6]): ~11 VALU ops per dword, no divergent LDS gathers.  Coefficient 1 is a plain XOR.
@@ -15,15 +17,6 @@
 #define TAMD_WAVES_PER_WG 4
 
 typedef unsigned long long u64;
-
-__device__ __forceinline__ uint32_t gf_mul4(uint32_t x, uint32_t t0lo, uint32_t t0hi, uint32_t t1lo,
-                                            uint32_t t1hi, uint32_t t2lo, uint32_t t2hi) {
-    const uint32_t s0 = x & 0x07070707u;
-    const uint32_t s1 = (x >> 3) & 0x07070707u;
-    const uint32_t s2 = (x >> 6) & 0x03030303u;
-    return __builtin_amdgcn_perm(t0hi, t0lo, s0) ^ __builtin_amdgcn_perm(t1hi, t1lo, s1) ^
-           __builtin_amdgcn_perm(t2hi, t2lo, s2);
-}
 
 __device__ __forceinline__ u64 byte_mask(uint32_t nbytes) {  // low `nbytes` bytes set (nbytes < 8)
     return (1ull << (8u * nbytes)) - 1ull;
@@ -47,6 +40,22 @@ __device__ __forceinline__ tamd_instr fetch_instr(const tamd_instr* __restrict__
         r.row = uniform(v.y);
         r.len = uniform(v.z);
         r.cap = uniform(v.w);
+        return r;
+    }
+}
+
+// An op record, the same two ways.
+template <bool LDSI>
+__device__ __forceinline__ tamd_op fetch_op(const tamd_op* __restrict__ p, uint32_t i) {
+    if constexpr (!LDSI) {
+        return p[i];
+    } else {
+        const uint4 v = *(const uint4*)(p + i);
+        tamd_op r;
+        r.first = uniform(v.x);
+        r.count = uniform(v.y);
+        r.span = uniform(v.z);
+        r.full = uniform(v.w);
         return r;
     }
 }
@@ -302,14 +311,43 @@ __device__ __forceinline__ void roll_rows(const uint8_t* rbase, size_t step, uin
     }
 }
 
-// ACCR: a strided run of equally long rows (program.h).  TAMD_RBATCH row loads are issued
-// together (the row index is clamped to the run, so no load is branched around); the per-row
-// table address stepping runs on the vector ALU: lane runs step the column value index
-// (cx = 3 + (199 col mod 253)) through the lane table, Cauchy runs fetch their inverses for the
-// whole batch first.
+// DENSE runs (program.h), the two pieces both forms share.  The coefficient of the row in column
+// c from a COEFS word: the lane-sum combination sd ^ rx * tp the recovery row reads, sd and tp
+// picked from 1, cx, cx^2 by the six opcode bits of the column's lane (c mod 8).
+__device__ __forceinline__ uint32_t dense_coef(const tamd_instr& cw, uint32_t c, const uint32_t* __restrict__ lds) {
+    const uint8_t* sqr = (const uint8_t*)(lds + TAMD_LDS_INV + 64u);
+    const PermT prx = perm_at(lds, ((cw.len >> 16) & 0xffu) * 8u);
+    const u64 opw = (u64)cw.row | ((u64)(cw.len & 0xffffu) << 32);
+    const uint32_t b = (uint32_t)(opw >> (6u * (c & 7u))) & 63u;
+    const uint32_t cx = 3u + (199u * (c % 253u)) % 253u, cx2 = sqr[cx];
+    const uint32_t sd = (b & 1u) ^ ((b & 2u) ? cx : 0u) ^ ((b & 4u) ? cx2 : 0u);
+    const uint32_t tp = ((b >> 3) & 1u) ^ ((b & 16u) ? cx : 0u) ^ ((b & 32u) ? cx2 : 0u);
+    return (sd ^ mul_sel(sel4(tp), prx)) & 0xffu;
+}
+// The ADJ entries after a COEFS word: coefficient additions for single rows (the LDPC pair
+// columns of the recovery row, SiameseEncoder.cpp:1100-1144, folded into the run).  They come
+// sorted by row (empty entries, row 0, only at the end), so a cursor walks the `n` of them once per
+// run: the block of 64 rows from `base` takes the ones below its end, lane j (`mine` = base + j)
+// adding its row's to g.
+template <bool LDSI>
+__device__ __forceinline__ uint32_t dense_adj(uint32_t g, const uint32_t* __restrict__ ad, uint32_t n, uint32_t& cur,
+                                              uint32_t base, uint32_t mine) {
+    for (; cur < n; ++cur) {
+        const uint32_t d = LDSI ? uniform(ad[cur]) : ad[cur];
+        if ((d >> 16) >= base + 64u) break;
+        if ((d >> 16) == mine) g ^= (d >> 8) & 0xffu;
+    }
+    return g;
+}
+
+// ACCR: a strided run of equally long rows (program.h).  Every mode takes its rows from
+// roll_rows, TAMD_RBATCH at a time (the row index is clamped to the run, so no load is branched
+// around), and differs in the body: what a row's coefficient is and which accumulators it goes
+// to.  The per-row table addresses are computed on the vector ALU: lane runs step the column
+// value index (cx = 3 + (199 col mod 253)) through the lane table, Cauchy rows read the product
+// tables of their inverse in one lookup.
 // Batches of rows are numbered across the op (`unit`); with nw > 1 waves sharing the op, a
-// wave combines only the batches with unit mod nw == wid (the coefficient stepping still walks
-// every row).
+// wave combines only the batches with unit mod nw == wid.
 template <bool FULL, int NH, uint32_t TAMD_RBATCH, bool LDSI = false>
 __device__ __forceinline__ void run_accr(const tamd_instr& a, const tamd_instr& r, const tamd_instr& tg,
                                          const tamd_instr* __restrict__ adj, uint32_t o, uint32_t ox,
@@ -324,121 +362,48 @@ __device__ __forceinline__ void run_accr(const tamd_instr& a, const tamd_instr& 
     const uint8_t* rbase = arena + (size_t)row0 * TAMD_ROW_UNIT;
     const uint32_t lo = load_off<FULL>(o, len), lox = NH == 3 ? load_off<false>(ox, len) : 0u;
     const size_t step = (size_t)stride * TAMD_ROW_UNIT;
-#define TAMD_RUN_LD(idx) lv_load_at<NH>(rbase + (size_t)(idx) * step, lo, lox)
-    // loads past the run's end re-read its last row (never consumed)
-#define TAMD_RUN_ROW(q) TAMD_RUN_LD(min(e + (q), count - 1u))
     if (mode == TAMD_R_LANE3) {
-        // byte offset of the (cx, cx^2) tables in the lane table: 48 bytes per column value index
+        // byte offset of the (cx, cx^2) tables in the lane table: 48 bytes per column value index,
+        // stepped once per row (never shared, program.h: roll_rows hands the rows over in order)
         const uint32_t W = 253u * 48u;
         uint32_t t = vgpr(((199u * (col0 % 253u)) % 253u) * 48u);
         const uint32_t tstep = vgpr(((199u * (cstep % 253u)) % 253u) * 48u);
-        if (nw == 1u) {
-            // Rolling loads: the rows of the next batch half are loaded as soon as a half has been
-            // combined, so a wave keeps 3-6 row loads in flight while it computes instead of
-            // waiting a full memory round trip per batch (same registers as a plain batch).
-            constexpr uint32_t H = TAMD_RBATCH / 2;
-            LV<NH> d[TAMD_RBATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q) d[q] = TAMD_RUN_LD(min(q, count - 1u));
-            for (uint32_t e = 0; e < count; e += TAMD_RBATCH) {
-                const bool more = e + TAMD_RBATCH < count;
-#pragma unroll
-                for (uint32_t h = 0; h < 2; ++h) {
-#pragma unroll
-                    for (uint32_t q = h * H; q < (h ? TAMD_RBATCH : H); ++q) {
-                        if (e + q < count) {
-                            const uint32_t ti = TAMD_LDS_LANE + (t >> 2);
-                            const PermT c1 = perm_at(lds, ti), c2 = perm_at_hi(lds, ti + 6u);
-                            lv_acc3<NH>(lv_keep<FULL, NH>(d[q], o, len, ox), c1, c2, a0, a1, a2);
-                            t += tstep;
-                            t = min(t, t - W);
-                        }
-                    }
-                    if (more) {
-#pragma unroll
-                        for (uint32_t q = h * H; q < (h ? TAMD_RBATCH : H); ++q)
-                            d[q] = TAMD_RUN_LD(min(e + TAMD_RBATCH + q, count - 1u));
-                    }
-                }
-            }
-            unit += (count + TAMD_RBATCH - 1) / TAMD_RBATCH;
-            return;
-        }
-        for (uint32_t e = 0; e < count; e += TAMD_RBATCH) {
-            if ((unit++ & (nw - 1u)) != wid) {
-#pragma unroll
-                for (uint32_t q = 0; q < TAMD_RBATCH; ++q) {
-                    t += tstep;
-                    t = min(t, t - W);
-                }
-                continue;
-            }
-            LV<NH> d[TAMD_RBATCH];
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q) d[q] = TAMD_RUN_ROW(q);
-#pragma unroll
-            for (uint32_t q = 0; q < TAMD_RBATCH; ++q) {
-                if (e + q < count) {
-                    const uint32_t ti = TAMD_LDS_LANE + (t >> 2);
-                    const PermT c1 = perm_at(lds, ti), c2 = perm_at_hi(lds, ti + 6u);
-                    lv_acc3<NH>(lv_keep<FULL, NH>(d[q], o, len, ox), c1, c2, a0, a1, a2);
-                    t += tstep;
-                    t = min(t, t - W);  // t - W wraps above t while t < W
-                }
-            }
-        }
+        roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
+                                         [&](uint32_t, const LV<NH>& v) __attribute__((always_inline)) {
+                                             const uint32_t ti = TAMD_LDS_LANE + (t >> 2);
+                                             const PermT c1 = perm_at(lds, ti), c2 = perm_at_hi(lds, ti + 6u);
+                                             lv_acc3<NH>(v, c1, c2, a0, a1, a2);
+                                             t += tstep;
+                                             t = min(t, t - W);  // t - W wraps above t while t < W
+                                         });
     } else if (mode == TAMD_R_MULTI) {
         // Up to three Cauchy / parity rows over overlapping windows: row i of the run goes to
-        // every target a with lo_a <= i < hi_a, loaded once (the op is never shared: nw == 1).
-        uint32_t col = vgpr(col0);
-        const uint32_t cs = vgpr(cstep);
+        // every target a with lo_a <= i < hi_a, loaded once (never shared either).
         const uint32_t w0 = tg.row, w1 = tg.len, w2 = tg.cap;
         // target a takes rows lo_a <= i < hi_a: (i - lo_a) < n_a, unsigned
         const uint32_t l0 = (w0 >> 10) & 0x7ffu, l1 = (w1 >> 10) & 0x7ffu, l2 = (w2 >> 10) & 0x7ffu;
         const uint32_t h0 = (w0 >> 21) - l0, h1 = (w1 >> 21) - l1, h2 = (w2 >> 21) - l2;
         const uint32_t x0 = ((w0 >> 2) & 0xffu) + 64u, x1 = ((w1 >> 2) & 0xffu) + 64u, x2 = ((w2 >> 2) & 0xffu) + 64u;
         const bool k0 = (w0 & 3u) == TAMD_R_CONST, k1 = (w1 & 3u) == TAMD_R_CONST, k2 = (w2 & 3u) == TAMD_R_CONST;
-        constexpr uint32_t H = TAMD_RBATCH / 2;
-        LV<NH> d[TAMD_RBATCH];
-#pragma unroll
-        for (uint32_t q = 0; q < TAMD_RBATCH; ++q) d[q] = TAMD_RUN_LD(min(q, count - 1u));
-#define TAMD_MULTI_TARGET(l, h, k, x, acc)                                                 \
-    if (i - l < h) {                                                                       \
-        if (k) acc ^= v;                                                                   \
-        else acc ^= lv_mul<NH>(v, perm_at(lds, TAMD_LDS_CINV - 512u + (((col & 63u) ^ x) << 3)));  \
-    }
-        for (uint32_t e = 0; e < count; e += TAMD_RBATCH) {
-            const bool more = e + TAMD_RBATCH < count;
-#pragma unroll
-            for (uint32_t h = 0; h < 2; ++h) {
-#pragma unroll
-                for (uint32_t q = h * H; q < (h ? TAMD_RBATCH : H); ++q) {
-                    const uint32_t i = e + q;
-                    if (i < count) {
-                        const LV<NH> v = lv_keep<FULL, NH>(d[q], o, len, ox);
-                        TAMD_MULTI_TARGET(l0, h0, k0, x0, a0)
-                        TAMD_MULTI_TARGET(l1, h1, k1, x1, a1)
-                        TAMD_MULTI_TARGET(l2, h2, k2, x2, a2)
-                    }
-                    col += cs;
-                }
-                if (more) {
-#pragma unroll
-                    for (uint32_t q = h * H; q < (h ? TAMD_RBATCH : H); ++q)
-                        d[q] = TAMD_RUN_LD(min(e + TAMD_RBATCH + q, count - 1u));
-                }
-            }
-        }
-#undef TAMD_MULTI_TARGET
-        unit += (count + TAMD_RBATCH - 1) / TAMD_RBATCH;
-        return;
+        roll_rows<FULL, NH, TAMD_RBATCH>(rbase, step, lo, lox, count, o, len, ox, unit, nw, wid,
+                                         [&](uint32_t i, const LV<NH>& v) __attribute__((always_inline)) {
+                                             const uint32_t c = (col0 + i * cstep) & 63u;  // (wave-uniform)
+                                             auto target = [&](uint32_t l, uint32_t h, bool k, uint32_t x, LV<NH>& acc)
+                                                               __attribute__((always_inline)) {
+                                                 if (i - l >= h) return;
+                                                 if (k) acc ^= v;
+                                                 else acc ^= lv_mul<NH>(v, perm_at(lds, TAMD_LDS_CINV - 512u + ((c ^ x) << 3)));
+                                             };
+                                             target(l0, h0, k0, x0, a0);
+                                             target(l1, h1, k1, x1, a1);
+                                             target(l2, h2, k2, x2, a2);
+                                         });
     } else if (!LDSI && mode == TAMD_R_DENSE && p > 1u) {  // (not in tamd_serve: Server::build)
         // p (2 or 3) Siamese rows of one encoder over nested sum ranges (program.h DENSE with
         // targets): every packet of the run is loaded once and multiplied by each target's
         // coefficient; target t takes rows i < hi_t into acc_t.  Coefficients as for one target
         // (below), 64 rows at a time, the column value shared by the targets.
         const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        const uint8_t* sqr = (const uint8_t*)(lds + TAMD_LDS_INV + 64u);
         // COEFS_t and its ADJ words: COEFS_0 is `tg`, the others follow the previous one's ADJ
         const uint32_t n0 = tg.cap & 0xffffu;
         const tamd_instr c1 = fetch_instr<LDSI>(adj, n0);
@@ -455,26 +420,10 @@ __device__ __forceinline__ void run_accr(const tamd_instr& a, const tamd_instr& 
             gblk = i >> 6;
             const uint32_t base = i & ~63u, mine = base + lane;
             const uint32_t c = (col0 + mine * cstep) & (TAMD_COLUMN_PERIOD - 1u);
-            const uint32_t cx = 3u + (199u * (c % 253u)) % 253u, cx2 = sqr[cx], sh = 6u * (c & 7u);
             // (the rx tables are read here, once per 64 rows, not kept across the rows)
-            auto one = [&](const tamd_instr& cw, const uint32_t* __restrict__ ad, uint32_t nadj,
-                           uint32_t& cur) __attribute__((always_inline)) -> uint32_t {
-                const PermT prx = perm_at(lds, ((cw.len >> 16) & 0xffu) * 8u);
-                const u64 opw = (u64)cw.row | ((u64)(cw.len & 0xffffu) << 32);
-                const uint32_t b = (uint32_t)(opw >> sh) & 63u;
-                const uint32_t sd = (b & 1u) ^ ((b & 2u) ? cx : 0u) ^ ((b & 4u) ? cx2 : 0u);
-                const uint32_t tp = ((b >> 3) & 1u) ^ ((b & 16u) ? cx : 0u) ^ ((b & 32u) ? cx2 : 0u);
-                uint32_t g = (sd ^ mul_sel(sel4(tp), prx)) & 0xffu;
-                for (; cur < 4u * nadj; ++cur) {
-                    const uint32_t d = LDSI ? uniform(ad[cur]) : ad[cur];
-                    if ((d >> 16) >= base + 64u) break;
-                    if ((d >> 16) == mine) g ^= (d >> 8) & 0xffu;
-                }
-                return g * 8u;
-            };
-            gv0 = one(tg, ad0, n0, cur0);
-            gv1 = one(c1, ad1, n1, cur1);
-            if (p > 2u) gv2 = one(c2, ad2, n2, cur2);
+            gv0 = 8u * dense_adj<LDSI>(dense_coef(tg, c, lds), ad0, 4u * n0, cur0, base, mine);
+            gv1 = 8u * dense_adj<LDSI>(dense_coef(c1, c, lds), ad1, 4u * n1, cur1, base, mine);
+            if (p > 2u) gv2 = 8u * dense_adj<LDSI>(dense_coef(c2, c, lds), ad2, 4u * n2, cur2, base, mine);
         };
         // row i (its slice bytes v) into every target whose range holds it, one product table
         // live at a time
@@ -499,41 +448,24 @@ __device__ __forceinline__ void run_accr(const tamd_instr& a, const tamd_instr& 
         // its product table at the index broadcast from its lane, so no row waits on the LDS
         // round trips of its own coefficient.
         const bool dense = mode == TAMD_R_DENSE;
-        const u64 opw = (u64)tg.row | ((u64)(tg.len & 0xffffu) << 32);
-        // DENSE w0 bits 24..31: s > 1 scales every coefficient (a decoder's scaled elimination run)
-        const uint32_t dscale = dense ? a.w0 >> 24 : 0u;
-        const PermT prx = perm_at(lds, (dense ? (tg.len >> 16) & 0xffu : a.w0 >> 24) * 8u);
-        const uint8_t* sqr = (const uint8_t*)(lds + TAMD_LDS_INV + 64u);
+        // w0 bits 24..31: the scale s (DENSE: s > 1 scales every coefficient, a decoder's scaled
+        // elimination run)
+        const uint32_t scale = a.w0 >> 24;
         const uint8_t* inv = (const uint8_t*)(lds + TAMD_LDS_INV);
         const uint32_t px = p + 64u;
         const uint32_t lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
-        auto coef = [&](uint32_t c) -> uint32_t {
-            if (!dense) return mul_sel(sel4(inv[(c & 63u) ^ px]), prx) & 0xffu;
-            const uint32_t b = (uint32_t)(opw >> (6u * (c & 7u))) & 63u;
-            const uint32_t cx = 3u + (199u * (c % 253u)) % 253u, cx2 = sqr[cx];
-            const uint32_t sd = (b & 1u) ^ ((b & 2u) ? cx : 0u) ^ ((b & 4u) ? cx2 : 0u);
-            const uint32_t tp = ((b >> 3) & 1u) ^ ((b & 16u) ? cx : 0u) ^ ((b & 32u) ? cx2 : 0u);
-            return (sd ^ mul_sel(sel4(tp), prx)) & 0xffu;
-        };
-        // DENSE: COEFS.cap ADJ words follow, coefficient additions for single rows (the LDPC pair
-        // columns of the recovery row, SiameseEncoder.cpp:1100-1144, folded into the run)
-        // The additions come sorted by row (empty entries, row 0, only at the end): a cursor walks
-        // them once per run, each block taking the ones below its end.
+        // DENSE: COEFS.cap ADJ words follow
         const uint32_t nadj = dense ? 4u * tg.cap : 0u;
-        const uint32_t* __restrict__ adw = (const uint32_t*)adj;
         uint32_t acur = 0;
         uint32_t gv = 0, gblk = ~0u;  // gv: lane j's table index for row 64 * gblk + j
         auto row_tab = [&](uint32_t i) -> PermT {
             if ((i >> 6) != gblk) {
                 gblk = i >> 6;
                 const uint32_t base = i & ~63u, mine = base + lane;
-                uint32_t g = coef((col0 + mine * cstep) & (TAMD_COLUMN_PERIOD - 1u));
-                for (; acur < nadj; ++acur) {
-                    const uint32_t d = LDSI ? uniform(adw[acur]) : adw[acur];
-                    if ((d >> 16) >= base + 64u) break;
-                    if ((d >> 16) == mine) g ^= (d >> 8) & 0xffu;
-                }
-                if (dscale > 1u) g = mul_sel(sel4(g), perm_at(lds, dscale * 8u)) & 0xffu;
+                const uint32_t c = (col0 + mine * cstep) & (TAMD_COLUMN_PERIOD - 1u);
+                uint32_t g = dense ? dense_adj<LDSI>(dense_coef(tg, c, lds), (const uint32_t*)adj, nadj, acur, base, mine)
+                                   : inv[(c & 63u) ^ px];
+                if (scale > 1u) g = mul_sel(sel4(g), perm_at(lds, scale * 8u)) & 0xffu;
                 gv = g * 8u;
             }
             return perm_at(lds, (uint32_t)__builtin_amdgcn_readlane((int)gv, (int)(i & 63u)));
@@ -564,8 +496,6 @@ __device__ __forceinline__ void run_accr(const tamd_instr& a, const tamd_instr& 
                                          [&](uint32_t, const LV<NH>& v) __attribute__((always_inline)) { x ^= v; });
         a0 ^= plain ? x : lv_mul<NH>(x, cp);
     }
-#undef TAMD_RUN_ROW
-#undef TAMD_RUN_LD
 }
 
 // One work item: the op's instruction list over this wave's slice.  FULL items lie below every
@@ -668,6 +598,37 @@ __device__ __forceinline__ LV<NH> run_item(const tamd_instr* __restrict__ instrs
     return a0;
 }
 
+// A work item as its wave sees it: slice `slice` of op `op`.  o, ox: the lane's byte offsets in the
+// op's rows (LV: 16 bytes per lane below the slice's first 1024 bytes, NH = 3: 8 more past them);
+// full: the slice lies below every length the op uses.
+struct Item {
+    uint32_t first, end, o, ox;
+    bool full;
+};
+template <int NH>
+__device__ __forceinline__ Item item_of(const tamd_op& op, uint32_t slice, uint32_t lane) {
+    // bytes of a slice at the lanes' 16-byte offsets (NH = 3: the first 1024, FULL's extent)
+    constexpr uint32_t SLICE = 64u * 8u * NH, MAIN = NH == 3 ? 1024u : SLICE;
+    const uint32_t s0 = slice * SLICE;
+    Item w;
+    w.first = uniform(op.first);
+    w.end = uniform(op.first + op.count);
+    w.o = s0 + lane * 8u * (NH < 3 ? NH : 2);
+    w.ox = s0 + MAIN + lane * 8u;
+    w.full = s0 + MAIN <= uniform(op.full);
+    return w;
+}
+// ... and run: run_item with or without the per-lane length handling.
+template <int NH, uint32_t B, bool LDSI = false>
+__device__ __forceinline__ LV<NH> run_item_of(const Item& w, const tamd_instr* __restrict__ instrs, uint32_t lane,
+                                              uint8_t* __restrict__ arena, const uint8_t* __restrict__ zrow,
+                                              const uint32_t* __restrict__ lds, uint32_t nw, uint32_t wid,
+                                              LV<NH>* __restrict__ r1 = nullptr, LV<NH>* __restrict__ r2 = nullptr) {
+    const uint32_t laneb = lane * 8u * (NH < 3 ? NH : 2);  // (the zero row's bytes of a slot that loads no row)
+    return w.full ? run_item<true, NH, B, LDSI>(instrs, w.first, w.end, w.o, w.ox, laneb, arena, zrow, lds, nw, wid, r1, r2)
+                  : run_item<false, NH, B, LDSI>(instrs, w.first, w.end, w.o, w.ox, laneb, arena, zrow, lds, nw, wid, r1, r2);
+}
+
 // Ops of one level never read a row written by an op of the same level, so every load of a
 // batch can be issued before the batch's stores.  Persistent grid: each workgroup stages the
 // tables in LDS once and then claims items.  A slice is 64 lanes x 8*NH bytes.
@@ -681,15 +642,13 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
                                            uint32_t n_shared, uint8_t* __restrict__ arena,
                                            const uint32_t* __restrict__ gf_perm, const uint8_t* __restrict__ zrow,
                                            unsigned long long* __restrict__ stamps) {
-    constexpr uint32_t SLICE = 64u * 8u * NH;
-    // bytes of a slice at the lanes' 16-byte offsets (NH = 3: the first 1024, FULL's extent)
-    constexpr uint32_t MAIN = NH == 3 ? 1024u : SLICE;
     __shared__ __attribute__((aligned(16))) uint32_t lds_perm[TAMD_GF_DWORDS];
     __shared__ LV<NH> partial[TAMD_WAVES_PER_WG][64];  // shared ops: the waves' acc_0
     __shared__ uint32_t claim, shared_claim, shared_item;
     __shared__ tamd_segment lds_seg[TAMD_MAX_SEGMENTS];
     // the launch's items in the order waves take them: blocks of (segment, cost class) items,
-    // class by class across the segments (flags bit 0) or segment by segment; + a sentinel
+    // class by class across the segments, so the launch's long items (every level's class 0)
+    // are taken first; + a sentinel
     __shared__ uint4 lds_blk[TAMD_MAX_SEGMENTS * TAMD_COST_CLASSES + 1];  // {segment, first item, count, -}
     // this workgroup's items of block b: positions r_b, r_b + G, ... (.x = r_b, .y = how many)
     __shared__ uint2 lds_wg[TAMD_MAX_SEGMENTS * TAMD_COST_CLASSES + 1];
@@ -704,21 +663,14 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
             if (k >= sg.n) lds_seg[k].count = 0;
         }
         // (.w: the segment's first item in segment order, where the stamps of an item go)
-        uint32_t nb = 0, base = 0;
-        if (sg.flags & 1u) {
-            uint32_t first[TAMD_MAX_SEGMENTS] = {0, 0, 0, 0, 0, 0};
-            for (uint32_t c = 0; c < TAMD_COST_CLASSES; ++c) {
-                base = 0;
-                for (uint32_t k = 0; k < sg.n; ++k) {
-                    const uint32_t m = lds_seg[k].cls[c];
-                    if (m) lds_blk[nb++] = make_uint4(k, first[k], m, base);
-                    first[k] += m;
-                    base += lds_seg[k].count;
-                }
-            }
-        } else {
+        uint32_t nb = 0;
+        uint32_t first[TAMD_MAX_SEGMENTS] = {0, 0, 0, 0, 0, 0};
+        for (uint32_t c = 0; c < TAMD_COST_CLASSES; ++c) {
+            uint32_t base = 0;
             for (uint32_t k = 0; k < sg.n; ++k) {
-                if (lds_seg[k].count) lds_blk[nb++] = make_uint4(k, 0, lds_seg[k].count, base);
+                const uint32_t m = lds_seg[k].cls[c];
+                if (m) lds_blk[nb++] = make_uint4(k, first[k], m, base);
+                first[k] += m;
                 base += lds_seg[k].count;
             }
         }
@@ -752,8 +704,6 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
 
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = uniform(threadIdx.x >> 6);
-    const uint32_t laneb = lane * 8u * (NH < 3 ? NH : 2);
-    const uint32_t laneb_x = MAIN + lane * 8u;  // (NH = 3) the extension word's offset in the slice
 
     // Items [0, n_shared) are class-0 pure combines: the workgroup takes them one at a time
     // (items g, g + G, ...), each wave combining every fourth batch of rows; wave 0 reduces the
@@ -765,15 +715,11 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
         __syncthreads();  // every wave has read shared_item before it is claimed again
         if (it >= n_shared) break;
         const uint2 item = items[it];
-        const tamd_op op = ops[uniform(item.x)];
-        const uint32_t s0 = uniform(item.y) * SLICE;
-        const uint32_t o = s0 + laneb, ox = s0 + laneb_x;
-        const uint32_t first = uniform(op.first), end = uniform(op.first + op.count);
-        const bool full = s0 + MAIN <= uniform(op.full);
+        const Item w = item_of<NH>(ops[uniform(item.x)], uniform(item.y), lane);
+        const uint32_t first = w.first, end = w.end;
         const u64 t0 = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
         LV<NH> x1, x2;
-        const LV<NH> x = full ? run_item<true, NH, B>(instrs, first, end, o, ox, laneb, arena, zrow, lds_perm, TAMD_WAVES_PER_WG, wave, &x1, &x2)
-                              : run_item<false, NH, B>(instrs, first, end, o, ox, laneb, arena, zrow, lds_perm, TAMD_WAVES_PER_WG, wave, &x1, &x2);
+        const LV<NH> x = run_item_of<NH, B>(w, instrs, lane, arena, zrow, lds_perm, TAMD_WAVES_PER_WG, wave, &x1, &x2);
         // The op ends with one STORE + FOOTER per accumulator it fills: one for a pure combine, up
         // to three for a multi-target dense op; each is reduced through `partial` in turn.
         uint32_t nst = 1;
@@ -793,8 +739,8 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
                 sum ^= partial[2][lane];
                 sum ^= partial[3][lane];
                 const u64 foot = ((u64)f.len << 32) | f.row;
-                if (full) lv_store_row<true, NH>(arena, st.row, st.len, st.cap, foot, o, sum, ox);
-                else lv_store_row<false, NH>(arena, st.row, st.len, st.cap, foot, o, sum, ox);
+                if (w.full) lv_store_row<true, NH>(arena, st.row, st.len, st.cap, foot, w.o, sum, w.ox);
+                else lv_store_row<false, NH>(arena, st.row, st.len, st.cap, foot, w.o, sum, w.ox);
             }
         }
         if (wave == 0) {
@@ -828,15 +774,8 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
         const tamd_op* __restrict__ sops = (const tamd_op*)(pbase + uniform(sd.ops));
         const tamd_instr* __restrict__ ins = (const tamd_instr*)(pbase + uniform(sd.instrs));
         const uint2 item = ((const uint2*)(pbase + uniform(sd.items)))[uniform(rel)];
-        const tamd_op op = sops[uniform(item.x)];
-        const uint32_t s0 = uniform(item.y) * SLICE;
-        const uint32_t o = s0 + laneb, ox = s0 + laneb_x;
-        const uint32_t first = uniform(op.first), end = uniform(op.first + op.count);
         const u64 t0 = stamps ? __builtin_amdgcn_s_memrealtime() : 0;
-        if (s0 + MAIN <= uniform(op.full))
-            run_item<true, NH, B>(ins, first, end, o, ox, laneb, arena, zrow, lds_perm, 1u, 0u);
-        else
-            run_item<false, NH, B>(ins, first, end, o, ox, laneb, arena, zrow, lds_perm, 1u, 0u);
+        run_item_of<NH, B>(item_of<NH>(sops[uniform(item.x)], uniform(item.y), lane), ins, lane, arena, zrow, lds_perm, 1u, 0u);
         if (stamps && lane == 0) {  // profiling only (TONK_AMD_STAMPS): vector stores of 100 MHz stamps
             __atomic_signal_fence(__ATOMIC_SEQ_CST);
             const u64 t1 = __builtin_amdgcn_s_memrealtime();
@@ -847,10 +786,8 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
     }
 }
 
-// tamd_exec16: 16 B per lane, 1024-byte slices, 6 rows per load batch (94 VGPRs, 5 waves/SIMD).
-// Measured on the bench program (round 1): 61.6-62.2 us per launch, against 62.7-63.5 us for
-// 8 B per lane / 512-byte slices / 8-row batches and 67 us for 16 B per lane with 8-row batches
-// (108 VGPRs, 4 waves/SIMD); only this variant is built.
+// The two executor kernels; both are built, Device::init picks one for the process
+// (tonk_amd::slice_bytes()).  Each uses 106 SGPRs, which is what bounds the grid (Device::init).
 #define TAMD_EXEC_KERNEL(name, NH, B)                                                                  \
     extern "C" __global__ void __launch_bounds__(256)                                                   \
     name(const tamd_segments segments, const uint8_t* __restrict__ prog, uint32_t n_shared,            \
@@ -859,10 +796,14 @@ __device__ __forceinline__ void exec_level(const tamd_segments& sg, const uint8_
          unsigned long long* __restrict__ stamps) {                                                    \
         exec_level<NH, B>(segments, prog, n_shared, arena, gf_perm, zrow, stamps);                    \
     }
-TAMD_EXEC_KERNEL(tamd_exec16, 2, 6)
-// tamd_exec24: 1536-byte slices (16 + 8 B per lane), so a 1302-byte packet row is one work item
-// (program.h TAMD_SLICE_BYTES_X; chosen by Device::init, tonk_amd::slice_bytes()).
+// tamd_exec24, the default: 1536-byte slices (16 + 8 B per lane), so a 1302-byte packet row is
+// one work item (program.h TAMD_SLICE_BYTES_X); 5 rows per load batch, 4 waves/SIMD.
 TAMD_EXEC_KERNEL(tamd_exec24, 3, 5)
+// tamd_exec16 (TONK_AMD_SLICE=1024): 16 B per lane, 1024-byte slices, 6 rows per load batch,
+// 5 waves/SIMD.  Measured on the bench program (round 1): 61.6-62.2 us per launch, against
+// 62.7-63.5 us for 8 B per lane / 512-byte slices / 8-row batches and 67 us for 16 B per lane with
+// 8-row batches (108 VGPRs, 4 waves/SIMD).
+TAMD_EXEC_KERNEL(tamd_exec16, 2, 6)
 
 
 // ---------------------------------------------------------------------------------------------
@@ -892,7 +833,7 @@ __device__ __forceinline__ void vm_drain() { asm volatile("s_waitcnt vmcnt(0)" :
 
 // Copy `len` bytes between host memory (16-B aligned) and an arena row, one wave: 16 B per lane
 // per chunk, four chunks in flight per lane, the tail (len mod 16) byte by byte.
-template <bool TO_HOST, bool PLAIN = false>
+template <bool TO_HOST>
 __device__ __forceinline__ void serve_xfer(uint8_t* __restrict__ arena, u64 host, uint32_t unit, uint32_t len,
                                            uint32_t lane) {
     uint8_t* a = arena + (size_t)unit * TAMD_ROW_UNIT;
@@ -909,22 +850,19 @@ __device__ __forceinline__ void serve_xfer(uint8_t* __restrict__ arena, u64 host
         const uint4 v2 = *(const uint4*)(src + 16u * min(c2, m));
         const uint4 v3 = *(const uint4*)(src + 16u * min(c3, m));
         // Arena rows: write-through (agent scope), visible to the codec's next command on any
-        // XCD; host memory: system-scope stores, written through to the host before the completion
-        // word (plain stores there can still sit in the L2 when it is seen: wrong packets)
+        // XCD; host memory: plain stores, which can still sit in the L2 afterwards: the worker's
+        // release fence writes them back ahead of the completion word (8-byte system-scope stores,
+        // one fabric write each, made a recovery-packet read ~10x slower)
         const uint4 v[4] = {v0, v1, v2, v3};
 #pragma unroll
         for (uint32_t q = 0; q < 4; ++q)
             if (c0 + 64u * q < n16) {
                 uint8_t* d = dst + 16u * (c0 + 64u * q);
-                const u64 lo = ((u64)v[q].y << 32) | v[q].x, hi = ((u64)v[q].w << 32) | v[q].z;
-                if constexpr (PLAIN) {
+                if constexpr (TO_HOST) {
                     *(uint4*)d = v[q];
-                } else if constexpr (TO_HOST) {
-                    st_sys((uint64_t*)d, lo);
-                    st_sys((uint64_t*)(d + 8), hi);
                 } else {
-                    st_u64<true>(d, lo);
-                    st_u64<true>(d + 8, hi);
+                    st_u64<true>(d, ((u64)v[q].y << 32) | v[q].x);
+                    st_u64<true>(d + 8, ((u64)v[q].w << 32) | v[q].z);
                 }
             }
     }
@@ -969,9 +907,7 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
         // but t is handed on, the next poll looks ten slots further (up to 60 past t).
         if (threadIdx.x >= 64) return;
         const uint32_t lane = threadIdx.x, j = lane / TAMD_SERVE_GRANULES, k = lane - TAMD_SERVE_GRANULES * j;
-        // (A/B, pad bit 1: one slot per poll)
-        const uint32_t width = (a.pad & 2u) ? 1u : 10u;
-        const uint32_t wmask = (1u << width) - 1u;
+        constexpr uint32_t width = 10u, wmask = (1u << width) - 1u;  // slots per poll
         const bool mine = lane < width * TAMD_SERVE_GRANULES;
         u64 t = a.tail0, ahead = 0;  // ahead bit i: slot t + i handed on (bit 0 never set)
         uint32_t scan = 0;
@@ -1029,7 +965,6 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
 
     // ---- a worker ----
     constexpr int NH = 3;
-    constexpr uint32_t SLICE = 64u * 8u * NH, MAIN = 1024u;
     __shared__ __attribute__((aligned(16))) uint32_t lds_perm[TAMD_GF_DWORDS];
     __shared__ __attribute__((aligned(16))) uint4 cbuf[TAMD_SERVE_CMD_BYTES / 16];
     __shared__ u64 sh_cmd;
@@ -1038,7 +973,6 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uniform(tid >> 6);
     for (uint32_t i = tid; i < TAMD_GF_DWORDS / 4; i += TAMD_SERVE_THREADS)
         ((uint4*)lds_perm)[i] = ((const uint4*)a.gf)[i];
-    const uint32_t laneb = lane * 16u, laneb_x = MAIN + lane * 8u;
     const uint8_t* cb = (const uint8_t*)cbuf;
     // Wave 0 completes the previous command (its completion words) and claims the next one in
     // ONE wave-uniform region at the top of the loop, right before the barrier (a lane-divergent
@@ -1057,8 +991,8 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
                     st_sys(done + 1, prev_start);
                     st_sys(done + 2, __builtin_amdgcn_s_memrealtime());
                     // the reads' lines and anything else of the command still in the L2 go to
-                    // memory before the completion word (pad bit 0: no fence, A/B)
-                    if (!(a.pad & 1u)) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+                    // memory before the completion word
+                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
                     vm_drain();
                     st_sys(done + 3, prev_t[0]);
                     st_sys(done + 4, prev_t[1]);
@@ -1119,21 +1053,7 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
         const uint32_t cmd_bytes = uniform(sh_bytes);
         // 1. the command into LDS (8-byte system-scope loads: they bypass the L1, whose invalidation
         // runs meanwhile)
-        if (a.pad & 4u) {
-            vm_drain();
-            __syncthreads();
-            const uint32_t n16 = (cmd_bytes + 15u) >> 4, m = n16 - 1u;
-            const uint4* src = (const uint4*)cmd_addr;
-            constexpr uint32_t T = TAMD_SERVE_THREADS;
-            for (uint32_t b = tid; b < n16; b += 4u * T) {
-                const uint4 v0 = src[min(b, m)], v1 = src[min(b + T, m)], v2 = src[min(b + 2u * T, m)],
-                            v3 = src[min(b + 3u * T, m)];
-                cbuf[b] = v0;
-                if (b + T < n16) cbuf[b + T] = v1;
-                if (b + 2u * T < n16) cbuf[b + 2u * T] = v2;
-                if (b + 3u * T < n16) cbuf[b + 3u * T] = v3;
-            }
-        } else {
+        {
             const uint32_t n8 = (cmd_bytes + 7u) >> 3, m = n8 - 1u;
             const uint64_t* src = (const uint64_t*)cmd_addr;
             constexpr uint32_t T = TAMD_SERVE_THREADS;
@@ -1199,7 +1119,7 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
         prev_t[1] = __builtin_amdgcn_s_memrealtime();
         // 3. the program, level by level
         const tamd_instr* ins = (const tamd_instr*)(cb + uniform(c->off_instr));
-        const uint4* ops = (const uint4*)(cb + uniform(c->off_ops));
+        const tamd_op* ops = (const tamd_op*)(cb + uniform(c->off_ops));
         const uint2* items = (const uint2*)(cb + uniform(c->off_items));
         for (uint32_t l = 0; l < levels; ++l) {
             const uint32_t b0 = uniform(c->level_base[l]), b1 = uniform(c->level_base[l + 1]), n = b1 - b0;
@@ -1213,35 +1133,25 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
                 const uint32_t G = TAMD_SERVE_WAVES >> (32u - __builtin_clz(n - 1u | 1u) - (n == 1u ? 1u : 0u));
                 const uint32_t grp = wave / G, rank = wave % G;
                 const bool active = grp < n;
-                uint32_t shared = 0, full = 0, first = 0, end = 0, o = 0, ox = 0;
+                uint32_t shared = 0;
+                Item w = {0, 0, 0, 0, false};
                 LV<NH> x = lv_zero<NH>();
                 if (active) {
                     const uint2 item = items[b0 + grp];
-                    const uint4 op = ops[uniform(item.x)];
                     shared = uniform(item.y) >> 31;
-                    const uint32_t s0 = (uniform(item.y) & 0x7fffffffu) * SLICE;
-                    o = s0 + laneb;
-                    ox = s0 + laneb_x;
-                    first = uniform(op.x);
-                    end = first + uniform(op.y);
-                    full = s0 + MAIN <= uniform(op.w);
-                    if (shared || rank == 0) {
-                        const uint32_t nw = shared ? G : 1u, wid = shared ? rank : 0u;
-                        if (full)
-                            x = run_item<true, NH, 5, true>(ins, first, end, o, ox, laneb, a.arena, a.zrow, lds_perm, nw, wid);
-                        else
-                            x = run_item<false, NH, 5, true>(ins, first, end, o, ox, laneb, a.arena, a.zrow, lds_perm, nw, wid);
-                    }
+                    w = item_of<NH>(fetch_op<true>(ops, uniform(item.x)), uniform(item.y) & 0x7fffffffu, lane);
+                    if (shared || rank == 0)
+                        x = run_item_of<NH, 5, true>(w, ins, lane, a.arena, a.zrow, lds_perm, shared ? G : 1u, shared ? rank : 0u);
                 }
                 partial[wave][lane] = x;
                 __syncthreads();
                 if (active && shared && rank == 0) {
                     LV<NH> sum = x;
-                    for (uint32_t w = 1; w < G; ++w) sum ^= partial[wave + w][lane];
-                    const tamd_instr st = fetch_instr<true>(ins, end - 2u), f = fetch_instr<true>(ins, end - 1u);
+                    for (uint32_t q = 1; q < G; ++q) sum ^= partial[wave + q][lane];
+                    const tamd_instr st = fetch_instr<true>(ins, w.end - 2u), f = fetch_instr<true>(ins, w.end - 1u);
                     const u64 foot = ((u64)f.len << 32) | f.row;  // STORE (acc_0) + FOOTER end every pure op
-                    if (full) lv_store_row<true, NH, true>(a.arena, st.row, st.len, st.cap, foot, o, sum, ox);
-                    else lv_store_row<false, NH, true>(a.arena, st.row, st.len, st.cap, foot, o, sum, ox);
+                    if (w.full) lv_store_row<true, NH, true>(a.arena, st.row, st.len, st.cap, foot, w.o, sum, w.ox);
+                    else lv_store_row<false, NH, true>(a.arena, st.row, st.len, st.cap, foot, w.o, sum, w.ox);
                 }
                 vm_drain();
                 __syncthreads();
@@ -1255,14 +1165,8 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
                 it = uniform(rdl(it, 0));
                 if (it >= b1) break;
                 const uint2 item = items[it];
-                const uint4 op = ops[uniform(item.x)];
-                const uint32_t s0 = (uniform(item.y) & 0x7fffffffu) * SLICE;
-                const uint32_t o = s0 + laneb, ox = s0 + laneb_x;
-                const uint32_t first = uniform(op.x), end = first + uniform(op.y);
-                if (s0 + MAIN <= uniform(op.w))
-                    run_item<true, NH, 5, true>(ins, first, end, o, ox, laneb, a.arena, a.zrow, lds_perm, 1u, 0u);
-                else
-                    run_item<false, NH, 5, true>(ins, first, end, o, ox, laneb, a.arena, a.zrow, lds_perm, 1u, 0u);
+                run_item_of<NH, 5, true>(item_of<NH>(fetch_op<true>(ops, uniform(item.x)), uniform(item.y) & 0x7fffffffu, lane),
+                                         ins, lane, a.arena, a.zrow, lds_perm, 1u, 0u);
             }
             vm_drain();
             __syncthreads();
@@ -1272,11 +1176,7 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
         // 4. the reads into the caller's pinned buffer
         for (uint32_t r = wave; r < n_rd; r += TAMD_SERVE_WAVES) {
             const tamd_xfer x = lds_xfer(cb + uniform(c->off_rd), r);
-            // (plain stores into the host buffer, written back by the release fence ahead of the
-            // completion word: 8-byte system-scope stores, one fabric write each, made a
-            // recovery-packet read ~10x slower; pad bit 3 restores them for A/B)
-            if (a.pad & 8u) serve_xfer<true>(a.arena, x.host, x.unit, x.len, lane);
-            else serve_xfer<true, true>(a.arena, x.host, x.unit, x.len, lane);
+            serve_xfer<true>(a.arena, x.host, x.unit, x.len, lane);
         }
         vm_drain();
         __syncthreads();
@@ -1286,14 +1186,13 @@ extern "C" __global__ void __launch_bounds__(TAMD_SERVE_THREADS) tamd_serve(cons
     }
 }
 
-// GF self test: out[y * 256 + x] = x * y through the same v_perm path the executor uses.
+// GF self test: out[y * 256 + x] = x * y through the executor's own product (sel4 / mul_sel), the
+// tables read from memory as the executor reads them from its LDS copy.
 extern "C" __global__ void tamd_gf_selftest(const uint32_t* __restrict__ gf_perm, uint8_t* __restrict__ out) {
     const uint32_t y = blockIdx.x;
     const uint32_t x4 = threadIdx.x;  // 64 threads x 4 bytes
-    const uint32_t* t = &gf_perm[y * 8u];
     const uint32_t xs = (x4 * 4u) | ((x4 * 4u + 1u) << 8) | ((x4 * 4u + 2u) << 16) | ((x4 * 4u + 3u) << 24);
-    const uint32_t r = gf_mul4(xs, t[0], t[1], t[2], t[3], t[4], t[5]);
-    *(uint32_t*)(out + y * 256u + x4 * 4u) = r;
+    *(uint32_t*)(out + y * 256u + x4 * 4u) = mul_sel(sel4(xs), perm_at(gf_perm, y * 8u));
 }
 
 // PCG32 (SiameseTools.h:79-101), used to generate the synthetic payloads on the device.
@@ -1348,16 +1247,21 @@ extern "C" __global__ void tamd_gen_rows(const GenDesc* __restrict__ d, uint32_t
     for (uint32_t z = hb + len; z < cap; ++z) dst[z] = 0;
 }
 
+// `len` bytes from src to dst by one workgroup: 16-byte chunks (both 16-B aligned), then the tail
+// byte by byte.
+__device__ __forceinline__ void copy_row(uint8_t* dst, const uint8_t* src, uint32_t len) {
+    const uint32_t n16 = len / 16u;
+    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) ((uint4*)dst)[i] = ((const uint4*)src)[i];
+    for (uint32_t i = n16 * 16u + threadIdx.x; i < len; i += blockDim.x) dst[i] = src[i];
+}
+
 // Host staging (device.cpp d2h_gather): pack rows {arena row, bytes, output offset} into one
 // buffer for a single D2H copy.  One workgroup per row, 16-byte stores where aligned.
 extern "C" __global__ void tamd_gather_rows(const GatherDesc* __restrict__ d, uint32_t n,
                                             const uint8_t* __restrict__ arena, uint8_t* __restrict__ out) {
     const GatherDesc g = d[blockIdx.x];
-    const uint8_t* src = arena + (size_t)g.row * TAMD_ROW_UNIT;  // rows are 64-B aligned
-    uint8_t* dst = out + g.out;                                   // outputs are 16-B aligned
-    const uint32_t n16 = g.len / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) ((uint4*)dst)[i] = ((const uint4*)src)[i];
-    for (uint32_t i = n16 * 16u + threadIdx.x; i < g.len; i += blockDim.x) dst[i] = src[i];
+    // (rows are 64-B aligned, outputs 16-B aligned)
+    copy_row(out + g.out, arena + (size_t)g.row * TAMD_ROW_UNIT, g.len);
 }
 
 // Coalesced uploads of the siamese.h C ABI (Device::upload): packets staged back to back in one
@@ -1365,11 +1269,7 @@ extern "C" __global__ void tamd_gather_rows(const GatherDesc* __restrict__ d, ui
 extern "C" __global__ void tamd_scatter_rows(const ScatterDesc* __restrict__ d, uint32_t n,
                                              const uint8_t* __restrict__ in, uint8_t* __restrict__ arena) {
     const ScatterDesc g = d[blockIdx.x];
-    const uint8_t* src = in + g.src;
-    uint8_t* dst = arena + (size_t)g.row * TAMD_ROW_UNIT;
-    const uint32_t n16 = g.len / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) ((uint4*)dst)[i] = ((const uint4*)src)[i];
-    for (uint32_t i = n16 * 16u + threadIdx.x; i < g.len; i += blockDim.x) dst[i] = src[i];
+    copy_row(arena + (size_t)g.row * TAMD_ROW_UNIT, in + g.src, g.len);
 }
 
 // Zero-copy transfers between pinned host memory and the arena (Device::host_copy): one
@@ -1380,11 +1280,7 @@ tamd_host_copy(const HostCopyDesc* __restrict__ d, uint32_t n, uint8_t* __restri
     const HostCopyDesc c = d[blockIdx.x];
     uint8_t* a = arena + (size_t)c.unit * TAMD_ROW_UNIT;
     uint8_t* h = (uint8_t*)c.host;
-    uint8_t* dst = to_host ? h : a;
-    const uint8_t* src = to_host ? a : h;
-    const uint32_t n16 = c.len / 16u;
-    for (uint32_t i = threadIdx.x; i < n16; i += blockDim.x) ((uint4*)dst)[i] = ((const uint4*)src)[i];
-    for (uint32_t i = n16 * 16u + threadIdx.x; i < c.len; i += blockDim.x) dst[i] = src[i];
+    copy_row(to_host ? h : a, to_host ? a : h, c.len);
 }
 
 // A small program's upload (Device::close_program / run, below kSmallUpload bytes): two ranges of

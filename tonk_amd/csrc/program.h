@@ -61,6 +61,7 @@
 //     executor steps the column value index from col0 without reducing the column; LaneSums
 //     never merges packets across the wrap into one run, engine.h).  CAUCHY, CONST, MULTI and
 //     DENSE runs may cross it (the column enters mod 64, or is reduced mod 2^22).
+//     The stepping also needs the rows in order: a LANE3 run is never in an op that waves share.
 //   - CAUCHY (a run's p, a MULTI target's p): p < 192 (SiameseCommon.h kCauchyMaxRows; the
 //     executor's table of inverses holds x = p + 64 up to 255).
 //   - MULTI: a TARGETS word follows; a target is unused (the whole word 0), CAUCHY or CONST (p of a
@@ -159,10 +160,6 @@ typedef struct tamd_segment {
 typedef struct tamd_segments {
     tamd_segment s[TAMD_MAX_SEGMENTS];
     uint32_t n;
-    uint32_t flags;  // bit 0: items are taken class by class across the segments (the launch's
-                     // longest first), else segment by segment.  The host always sets it: it
-                     // never sends 0, and the executor's segment-by-segment branch only remains
-                     // so that the kernels' instructions stay as they were measured.
 } tamd_segments;
 
 static inline uint32_t tamd_w0(uint32_t kind, uint32_t arg, uint32_t arg2 = 0) {

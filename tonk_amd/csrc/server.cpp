@@ -47,7 +47,7 @@ bool Server::init(Device& dev, unsigned workers, unsigned ring_size, double idle
     while (ring_size_ < ring_size) ring_size_ <<= 1;
     workers_ = workers ? workers : 1;
     idle_ticks_ = (uint64_t)(idle_ms * 1e5);  // s_memrealtime: 100 MHz
-    if (const char* e = getenv("TONK_AMD_SERVE_DEBUG")) debug_ = (uint32_t)atoi(e);
+    if (const char* e = getenv("TONK_AMD_SERVE_DEBUG")) debug_ = (uint32_t)atoi(e) & 1u;
     if (const char* e = getenv("TONK_AMD_SERVE_STALL_POST_MS")) stall_post_ms_ = (uint32_t)atoi(e);
     if (const char* e = getenv("TONK_AMD_WAIT_SPIN_US")) spin_us_ = atof(e);
     if (const char* e = getenv("TONK_AMD_WAIT_YIELD_US")) yield_us_ = atof(e);
@@ -117,10 +117,6 @@ bool Server::launch_locked(uint64_t tail0) {
     a.ring_mask = ring_size_ - 1;
     a.wl_mask = ring_size_ - 1;
     a.gen = gen_.load() + 1;
-    // (A/B bits of TONK_AMD_SERVE_DEBUG >> 2: 1 no release fence before the completion word,
-    // 2 the dispatcher polls one slot at a time, 4 commands copied with plain 16-byte loads,
-    // 8 reads stored with system-scope 8-byte stores)
-    a.pad = debug_ >> 2;
     // the instance's claim counter and quit flag start from zero (stream order: after the
     // previous instance has ended)
     if (hipMemsetAsync(dstate_, 0, sizeof(tamd_serve_dev), st) != hipSuccess) return false;

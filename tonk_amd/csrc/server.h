@@ -97,8 +97,8 @@ private:
     std::atomic<bool> dead_{false};
     double timeout_us_ = 3e6;  // a command not completed after this long kills the server
     bool ensure_running();      // false (and the server dead) when a relaunch failed
-    uint32_t debug_ = 0;  // TONK_AMD_SERVE_DEBUG bits (diagnostics): 1 the probe's completion words in
-                          // the server's own coherent page, 4 a release fence before every completion word
+    uint32_t debug_ = 0;  // TONK_AMD_SERVE_DEBUG (diagnostics): 1 the probe's completion words in the
+                          // server's own coherent page; every other bit is ignored
     uint64_t* dbg_done_ = nullptr;
     // Test hook (TONK_AMD_SERVE_STALL_POST_MS): command 100's poster sleeps this long between
     // taking its ticket and writing its descriptor; commands completed meanwhile behind it are
