@@ -5,6 +5,11 @@ maximum compressed message size (Initialize), then `compress(message)` returns t
 block, or b"" when the message should be sent as is (the reference's writtenBytes = 0; the
 receiver then calls MessageDecompressor::InsertUncompressed).  `compress_batch` is the
 device-resident batch the bench measures: many independent streams in one kernel launch.
+
+`MessageDecompressor` mirrors tonk::MessageDecompressor (PacketCompression.h:210-260) the same
+way: `decompress(block)` restores a compressed block, `insert_uncompressed(message)` takes a
+message that was sent as is into the history; `decompress_batch` restores many streams in one
+launch and chains after `compress_batch` on the device.
 """
 from __future__ import annotations
 
@@ -33,6 +38,20 @@ def _lib() -> ctypes.CDLL:
         L.tamd_compress_batch_host.restype = ctypes.c_int
         L.tamd_compress_batch_host.argtypes = [vp, u64, u32, u32, ctypes.POINTER(u32), u32, vp, ctypes.POINTER(u32),
                                                u32, ctypes.POINTER(ctypes.c_float)]
+        i32p, u8p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
+        L.tamd_decompressor_create.restype = vp
+        L.tamd_decompressor_create.argtypes = [ctypes.c_uint]
+        L.tamd_decompressor_insert_uncompressed.restype = None
+        L.tamd_decompressor_insert_uncompressed.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint]
+        L.tamd_decompressor_decompress.restype = ctypes.c_int
+        L.tamd_decompressor_decompress.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_uint,
+                                                   ctypes.POINTER(ctypes.c_uint)]
+        L.tamd_decompressor_destroy.restype = None
+        L.tamd_decompressor_destroy.argtypes = [vp]
+        for f in (L.tamd_decompress_batch, L.tamd_decompress_batch_host):
+            f.restype = ctypes.c_int
+            f.argtypes = [vp, u32, u32, ctypes.POINTER(u32), u8p, u32, vp, ctypes.POINTER(u32), i32p,
+                          ctypes.POINTER(ctypes.c_float)]
         _bound = True
     return L
 
@@ -97,3 +116,73 @@ def compress_batch_host(data, stride: int, n_streams: int, n_msgs: int, lens, ma
     if rc != 0:
         raise RuntimeError(f"tonk_amd: compress_batch_host failed (rc={rc})")
     return out.raw, list(W), ms.value
+
+
+class MessageDecompressor:
+    """tonk::MessageDecompressor on the GPU.  Raises when no gfx950 device is usable; after a
+    block fails to decode every later call raises too (the reference's connection closes)."""
+
+    def __init__(self, max_compressed_message_bytes: int):
+        self.max = int(max_compressed_message_bytes)
+        self._h = _lib().tamd_decompressor_create(self.max)
+        if not self._h:
+            raise RuntimeError("tonk_amd: tamd_decompressor_create failed (no gfx950 device, or bad size)")
+        self._dest = ctypes.create_string_buffer(self.max)
+
+    def decompress(self, block: bytes) -> bytes:
+        r = ctypes.c_uint(0)
+        rc = _lib().tamd_decompressor_decompress(self._h, block, len(block), self._dest, self.max, ctypes.byref(r))
+        if rc != 0:
+            raise RuntimeError(f"tonk_amd: decompress failed (rc={rc})")
+        return self._dest.raw[:r.value]
+
+    def insert_uncompressed(self, message: bytes) -> None:
+        _lib().tamd_decompressor_insert_uncompressed(self._h, message, len(message))
+
+    def close(self) -> None:
+        if self._h:
+            _lib().tamd_decompressor_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def decompress_batch(dev_in: int, n_streams: int, n_msgs: int, in_bytes, is_block, max_bytes: int, dev_out: int):
+    """Restore every message of `n_streams` fresh streams (device pointers from the caller): slot
+    i = s * n_msgs + k of `max_bytes` holds in_bytes[i] bytes, a compressed block where
+    is_block[i], else the message itself; 32 readable bytes follow the last input slot.  Returns
+    (restored bytes per message, status per message -- 0 or the negative reason -- as numpy
+    arrays; kernel ms)."""
+    import numpy as np
+    total = n_streams * n_msgs
+    N = np.ascontiguousarray(in_bytes, dtype=np.uint32)
+    B = np.ascontiguousarray(np.asarray(is_block) != 0, dtype=np.uint8)
+    assert N.size == total and B.size == total
+    R = np.zeros(total, dtype=np.uint32)
+    S = np.zeros(total, dtype=np.int32)
+    ms = ctypes.c_float(0.0)
+    rc = _lib().tamd_decompress_batch(dev_in, n_streams, n_msgs, N.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                      B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), max_bytes, dev_out,
+                                      R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                      S.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"tonk_amd: decompress_batch failed (rc={rc})")
+    return R, S, ms.value
+
+
+def decompress_batch_host(data, n_streams: int, n_msgs: int, in_bytes, is_block, max_bytes: int):
+    """decompress_batch from a host buffer of n_streams * n_msgs slots: returns (the output slots,
+    restored per message, status per message, kernel ms)."""
+    total = n_streams * n_msgs
+    N = (ctypes.c_uint32 * total)(*in_bytes)
+    B = (ctypes.c_uint8 * total)(*[1 if b else 0 for b in is_block])
+    R = (ctypes.c_uint32 * total)()
+    S = (ctypes.c_int32 * total)()
+    src = ctypes.create_string_buffer(bytes(data), total * max_bytes)
+    out = ctypes.create_string_buffer(total * max_bytes)
+    ms = ctypes.c_float(0.0)
+    rc = _lib().tamd_decompress_batch_host(src, n_streams, n_msgs, N, B, max_bytes, out, R, S, ctypes.byref(ms))
+    if rc != 0:
+        raise RuntimeError(f"tonk_amd: decompress_batch_host failed (rc={rc})")
+    return out.raw, list(R), list(S), ms.value

@@ -2,12 +2,12 @@
 // of zstd's predefined distributions, MessageCompressor's history-ring bookkeeping, and the
 // launches of tamd_lz_compress (lz.hip).
 #include "../../include/tonk_compress.h"
+#include "combine.h"
 #include "lz.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
-#include <condition_variable>
 #include <mutex>
 #include <stdio.h>
 #include <stdlib.h>
@@ -112,30 +112,17 @@ struct Compressor {
 
 using namespace tamd;
 
-// ---- the per-message drop-in: concurrent calls combined into one launch ----
-//
-// Tonk compresses each message on the connection's own thread and waits for the result
-// (PacketCompression.cpp:70-118).  One GPU round trip per message is slow next to zstd on the
-// calling thread, so calls from different connections are combined: a caller queues its
-// request; the first caller becomes the leader and runs every queued request as ONE batch (one
+// ---- the per-message drop-in: concurrent calls combined into one launch (combine.h): one
 // upload of all messages and descriptors, a scatter into the compressors' rings, one compression
-// launch with a wave per message, one download), then completes them and serves the requests
-// that queued meanwhile.  A batch costs about one round trip however many connections it serves.
+// launch with a wave per message, one download ----
 namespace {
-struct LzRequest {
-    Compressor* c;
+struct LzRequest : CombineRequest<Compressor> {
     const uint8_t* data;
     uint32_t bytes;
     uint8_t* dest;
     unsigned* written;
-    int rc = 0;
-    bool done = false;
-    std::condition_variable cv;  // its caller waits here: a batch wakes only its own callers
 };
-std::mutex g_req_mu;
-std::condition_variable g_req_cv;  // tamd_compressor_destroy waits here for its last call
-std::vector<LzRequest*> g_pending;
-bool g_leader = false;
+Combiner<LzRequest> g_combiner;
 
 // leader-only launch state (grown on demand)
 struct LzBatchState {
@@ -320,11 +307,7 @@ extern "C" void* tamd_compressor_create(unsigned max_bytes) {
 extern "C" void tamd_compressor_destroy(void* cp) {
     Compressor* c = (Compressor*)cp;
     if (!c) return;
-    {
-        // (no call of this compressor is queued or in flight: its owner is not calling it)
-        std::unique_lock<std::mutex> g(g_req_mu);
-        g_req_cv.wait(g, [c] { return !c->queued; });
-    }
+    g_combiner.wait_idle(c);  // (no call of this compressor is queued or in flight)
     if (c->ring) {  // (no launch reads it any more: its last call was waited for)
         std::lock_guard<std::mutex> g(g_ring_mu);
         g_free_rings.push_back(std::make_pair(c->device, c->ring));
@@ -344,41 +327,7 @@ extern "C" int tamd_compressor_compress(void* cp, const uint8_t* data, unsigned 
     req.bytes = bytes;
     req.dest = dest;
     req.written = written;
-    std::unique_lock<std::mutex> lk(g_req_mu);
-    g_pending.push_back(&req);
-    // Wait while another caller leads; take over when it steps down with this request unserved.
-    req.cv.wait(lk, [&req] { return req.done || !g_leader; });
-    if (req.done) return req.rc;
-    g_leader = true;
-    std::vector<LzRequest*> batch, later;
-    // The leader serves batches only until its own request is done, then hands leadership to a
-    // waiting caller: its own send path is never held by other connections' traffic.
-    while (!req.done) {
-        // one request per compressor and one device per batch (a compressor's messages are
-        // placed in its ring in call order); the rest waits for the next batch
-        batch.clear();
-        later.clear();
-        for (LzRequest* r : g_pending) {
-            if (r->c->queued || r->c->device != g_pending[0]->c->device) later.push_back(r);
-            else {
-                r->c->queued = true;
-                batch.push_back(r);
-            }
-        }
-        g_pending.swap(later);
-        lk.unlock();
-        run_batch(batch);
-        lk.lock();
-        for (LzRequest* r : batch) {
-            r->c->queued = false;
-            r->done = true;
-            if (r != &req) r->cv.notify_one();
-        }
-        g_req_cv.notify_all();
-    }
-    g_leader = false;
-    if (!g_pending.empty()) g_pending.front()->cv.notify_one();  // the next queued caller leads
-    return req.rc;
+    return g_combiner.submit(req, run_batch);
 }
 
 extern "C" int tamd_compress_batch(const void* dev_data, uint64_t stride, uint32_t n_streams, uint32_t n_msgs,
