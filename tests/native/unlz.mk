@@ -11,10 +11,10 @@ REF := -L$(ROOT)/oracle/_ref -lmsgcodec_ref -Wl,-rpath,'$$ORIGIN/../../../oracle
 
 all: _build/unlz_check _build/unlz_check_san
 
-_build/unlz_check: unlz_check.cpp $(CSRC)/unlz.h $(CSRC)/lz.h $(ROOT)/oracle/_ref/libmsgcodec_ref.so | _build
+_build/unlz_check: unlz_check.cpp lz_host.h $(CSRC)/unlz.h $(CSRC)/lz.h $(ROOT)/oracle/_ref/libmsgcodec_ref.so | _build
 	$(CXX) $(CXXFLAGS) -o $@ unlz_check.cpp $(REF)
 
-_build/unlz_check_san: unlz_check.cpp $(CSRC)/unlz.h $(CSRC)/lz.h $(ROOT)/oracle/_ref/libmsgcodec_ref.so | _build
+_build/unlz_check_san: unlz_check.cpp lz_host.h $(CSRC)/unlz.h $(CSRC)/lz.h $(ROOT)/oracle/_ref/libmsgcodec_ref.so | _build
 	$(CXX) $(CXXFLAGS) -O1 -fsanitize=address,undefined -static-libasan -static-libubsan -fno-sanitize-recover=undefined -fno-omit-frame-pointer -o $@ unlz_check.cpp $(REF)
 
 _build:

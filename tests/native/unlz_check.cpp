@@ -20,12 +20,16 @@
 //       timed, the median repetition is reported.
 //   unlz_check tables
 //       the decode-table build's phases for 64 lanes against the state-by-state build.
+//   unlz_check ring
+//       the compressor's form of the history-ring rule (lz.h RingTrack) and the decoder's
+//       (tamd_unlz_place) side by side: 10 maximum sizes x 200 seeded streams x 400 lengths.
 //
 // Stream files: "UNLZ", u32 streams; per stream u32 max, u32 messages; per message u32 is_block,
 // u32 bytes, the bytes.  Case files add per message i32 status, u32 restored, the restored bytes.
 static unsigned long long g_cnt[64];
 #define TAMD_UNLZ_COUNT(what) (++g_cnt[what])
 #include "../../tonk_amd/csrc/unlz.h"
+#include "lz_host.h"
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -242,8 +246,8 @@ static bool repeat_rewrite(const Bytes& b, Bytes* out) {
     return true;
 }
 
-// ---- the GPU compressor's format: lz.h's host block writer under a greedy parse (as
-// tests/native/lz_check.cpp drives it), over the linear stream with compress.cpp's ring rule.
+// ---- the GPU compressor's format: the host compressor of lz_host.h (as tests/native/lz_check.cpp
+// drives it) over the linear stream, with the guards a stream of any maximum needs.
 static std::vector<Msg> gpu_format_blocks(const Stream& st) {
     std::vector<Msg> res;
     uint8_t fse[TAMD_FSE_BYTES];
@@ -251,109 +255,24 @@ static std::vector<Msg> gpu_format_blocks(const Stream& st) {
     Bytes stream;
     for (const Msg& m : st.msgs) stream.insert(stream.end(), m.data.begin(), m.data.end());
     stream.resize(stream.size() + 16);
-    const uint32_t kMax = st.max;
-    unsigned next = 0;
-    uint64_t lin = 0, seg = 0, prev = 0;
-    bool have_prev = false;
+    RingTrack ring;
+    ring.max = st.max;
+    LzHostOptions opt;
+    opt.floor = 16;
+    opt.len_cap = 60000;
+    opt.max = st.max;
     std::vector<int64_t> table(1u << 14, -1);
+    Bytes out;
     for (const Msg& m : st.msgs) {
-        const uint32_t n = (uint32_t)m.data.size();
-        if (next + kMax > TAMD_UNLZ_RING) {
-            if (next) {
-                prev = seg;
-                have_prev = true;
-                seg = lin;
-            }
-            next = 0;
-        }
-        const uint64_t pos = lin;
-        uint64_t win = seg;
-        if (have_prev) win = prev + next + n < seg ? prev + next + n : seg;
-        std::vector<uint32_t> lo, off;
-        const uint8_t* s = stream.data();
-        auto hash = [&](uint64_t p) {
-            uint32_t w;
-            memcpy(&w, s + p, 4);
-            return (w * 2654435761u) >> 18;
-        };
-        uint32_t lit_start = 0, i = 0;
-        while (i + 4 <= n) {
-            const uint64_t p = pos + i;
-            const int64_t c = table[hash(p)];
-            table[hash(p)] = (int64_t)p;
-            uint32_t len = 0;
-            if (c >= 0 && (uint64_t)c >= win && (uint64_t)c < p)
-                while (len < n - i && len < 60000 && s[c + len] == s[p + len]) ++len;
-            if (len >= 4 && i - lit_start < 60000) {
-                lo.push_back((i - lit_start) | (len << 16));
-                off.push_back((uint32_t)(p - (uint64_t)c));
-                for (uint32_t j = 1; j < len && i + j + 4 <= n; ++j) table[hash(p + j)] = (int64_t)(p + j);
-                i += len;
-                lit_start = i;
-            } else {
-                ++i;
-            }
-        }
-        Bytes out(2 * (size_t)n + 256);
-        unsigned w = 0;
-        if (!lo.empty() && n >= 16) {
-            uint32_t lits = n - lit_start;
-            for (uint32_t v : lo) lits += v & 0xffffu;
-            Bytes litbuf;
-            uint32_t src = 0;
-            for (size_t q = 0; q <= lo.size(); ++q) {
-                const uint32_t ll = q < lo.size() ? (lo[q] & 0xffffu) : n - lit_start;
-                litbuf.insert(litbuf.end(), s + pos + src, s + pos + src + ll);
-                if (q < lo.size()) src += ll + (lo[q] >> 16);
-            }
-            uint32_t count[TAMD_HUF_SYMS] = {0};
-            bool small = true;
-            for (uint8_t c : litbuf) {
-                if (c >= TAMD_HUF_SYMS) small = false;
-                else ++count[c];
-            }
-            uint8_t h[4];
-            const uint32_t raw = tamd_lits_header(lits, out.data()) + lits;
-            uint32_t huf = 0;
-            Bytes hsec(raw + 64);
-            if (small) huf = tamd_huf_section(litbuf.data(), lits, count, hsec.data(), raw);
-            if (huf && huf < raw) {
-                memcpy(out.data(), hsec.data(), huf);
-                w = huf;
-            } else {
-                w = tamd_lits_header(lits, out.data());
-                memcpy(&out[w], litbuf.data(), lits);
-                w += lits;
-            }
-            const uint32_t hs = tamd_seq_header((uint32_t)lo.size(), h);
-            tamd_seq_tables tt;
-            std::vector<uint32_t> codes(lo.size());
-            for (size_t q = 0; q < lo.size(); ++q)
-                codes[q] = tamd_ll_code(lo[q] & 0xffffu) | (tamd_ml_code(lo[q] >> 16) << 8) |
-                           ((31u - (uint32_t)__builtin_clz(off[q] + 3u)) << 16);
-            tamd_seq_choose(codes.data(), (uint32_t)codes.size(), fse, &tt);
-            h[hs - 1] = (uint8_t)tamd_modes_byte(tt.mode);
-            memcpy(&out[w], h, hs);
-            w += hs;
-            const uint32_t order[3] = {0u, 2u, 1u};
-            for (uint32_t k : order) {
-                memcpy(&out[w], tt.desc[k], tt.desc_len[k]);
-                w += tt.desc_len[k];
-            }
-            if (w < n - 1) {
-                const uint32_t nb = tamd_fse_sequences_t(lo.data(), off.data(), (uint32_t)lo.size(), fse, &tt, &out[w], n - 1 - w);
-                w = nb ? w + nb : 0;
-            } else {
-                w = 0;
-            }
-        }
+        uint64_t pos = 0, win = 0;
+        ring.place((uint32_t)m.data.size(), &pos, &win);
+        LzHostStats hs;
+        const uint32_t w = lz_host_block(stream.data(), pos, (uint32_t)m.data.size(), win, table, fse, opt, &out, &hs);
         Msg b;
-        b.is_block = w && w < n && w <= kMax;
-        if (b.is_block) b.data.assign(out.begin(), out.begin() + w);
+        b.is_block = w != 0;
+        if (w) b.data.assign(out.begin(), out.begin() + w);
         else b.data = m.data;
         res.push_back(b);
-        next += n;
-        lin += n;
     }
     return res;
 }
@@ -860,10 +779,53 @@ static int mode_tables() {
     return 0;
 }
 
+// ---- the two forms of the ring rule ----------------------------------------------------------
+// RingTrack (lz.h: the compressor's linear positions and window start) and tamd_unlz_place (the
+// decoder's ring offset and dictionary length) stepped side by side over seeded message lengths.
+static int mode_ring() {
+    const uint32_t sizes[] = {1, 7, 1300, 4000, 8000, 11999, 12000, 12001, 23999, 24000};
+    unsigned long long placements = 0, restarts = 0, partial = 0;
+    for (uint32_t max : sizes)
+        for (uint32_t stream = 0; stream < 200; ++stream) {
+            uint32_t rng = max * 1000u + stream;
+            auto rnd = [&rng]() {
+                rng = rng * 1664525u + 1013904223u;
+                return rng >> 8;
+            };
+            RingTrack rt;
+            rt.max = max;
+            tamd_unlz_state S;
+            tamd_unlz_reset(&S);
+            uint64_t lin = 0;
+            for (uint32_t k = 0; k < 400; ++k) {
+                // uniform in 1..max; a fifth of the lengths forced to max, a seventh to 1
+                const uint32_t kind = rnd() % 35u;
+                const uint32_t n = kind < 7u ? max : kind < 12u ? 1u : 1u + rnd() % max;
+                uint64_t pos = 0, win = 0;
+                rt.place(n, &pos, &win);
+                const uint32_t before = S.next;
+                tamd_unlz_place(&S, max);
+                restarts += before != 0 && S.next == 0;
+                if (pos != lin) return fail("ring: position is not the running byte count", max, k);
+                if (S.next + n > TAMD_UNLZ_RING) return fail("ring: message placed past the ring's end", max, k);
+                const uint64_t seg = lin - S.next;
+                const uint32_t left = S.dict_len > S.next + n ? S.dict_len - (S.next + n) : 0u;
+                if (win != seg - left) return fail("ring: window start differs from the decoder's history", max, k);
+                partial += left != 0;
+                ++placements;
+                S.next += n;
+                lin += n;
+            }
+        }
+    printf("placements %llu, restarts %llu, partly overwritten dictionary %llu\nok\n", placements, restarts, partial);
+    return 0;
+}
+
 int main(int argc, char** argv) {
     if (argc >= 2 && std::string(argv[1]) == "tables") return mode_tables();
+    if (argc >= 2 && std::string(argv[1]) == "ring") return mode_ring();
     if (argc < 3) {
-        printf("usage: unlz_check tables | check|mutants|bench <streams> ...\n");
+        printf("usage: unlz_check tables | ring | check|mutants|bench <streams> ...\n");
         return 2;
     }
     std::vector<Stream> streams;

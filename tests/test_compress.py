@@ -9,115 +9,15 @@ reported beside the reference compressor's.
 """
 from __future__ import annotations
 
-import ctypes
 import os
 import subprocess
 
 import numpy as np
 import pytest
 
-from conftest import NATIVE, ROOT, _make
-
-REF = os.path.join(ROOT, "oracle", "_ref", "libmsgcodec_ref.so")
-MAX = 1300  # kMaxCompressedBytes of TonkUnitTest.cpp:604 (Tonk's datagram budget)
-
-
-def ref_lib():
-    if not os.path.exists(REF):
-        pytest.skip("oracle/_ref/libmsgcodec_ref.so not built (needs /root/reference at build time)")
-    L = ctypes.CDLL(REF)
-    vp, cu = ctypes.c_void_p, ctypes.c_uint
-    L.ref_comp_new.restype = vp
-    L.ref_comp_new.argtypes = [cu]
-    L.ref_comp.restype = ctypes.c_int
-    L.ref_comp.argtypes = [vp, ctypes.c_char_p, cu, ctypes.c_void_p, ctypes.POINTER(cu)]
-    L.ref_comp_free.argtypes = [vp]
-    L.ref_decomp_new.restype = vp
-    L.ref_decomp_new.argtypes = [cu]
-    L.ref_insert.argtypes = [vp, ctypes.c_char_p, cu]
-    L.ref_decomp.restype = ctypes.c_int
-    L.ref_decomp.argtypes = [vp, ctypes.c_char_p, cu, ctypes.c_void_p, cu]
-    L.ref_decomp_free.argtypes = [vp]
-    return L
-
-
-class RefDecompressor:
-    def __init__(self, L, max_bytes=MAX):
-        self.L, self.h = L, L.ref_decomp_new(max_bytes)
-        self.buf = ctypes.create_string_buffer(max_bytes + 64)
-
-    def feed(self, block: bytes, original: bytes) -> bytes:
-        """Tonk's receive side: Decompress a compressed block, InsertUncompressed otherwise."""
-        if not block:
-            self.L.ref_insert(self.h, original, len(original))
-            return original
-        n = self.L.ref_decomp(self.h, block, len(block), self.buf, len(self.buf))
-        assert n >= 0, "reference zstd rejected the block"
-        return self.buf.raw[:n]
-
-
-class RefCompressor:
-    def __init__(self, L, max_bytes=MAX):
-        self.L, self.h = L, L.ref_comp_new(max_bytes)
-        self.buf = ctypes.create_string_buffer(max_bytes + 64)
-
-    def compress(self, msg: bytes) -> bytes:
-        w = ctypes.c_uint(0)
-        assert self.L.ref_comp(self.h, msg, len(msg), self.buf, ctypes.byref(w)) == 0
-        return self.buf.raw[:w.value]
-
-
-class Pcg:
-    """siamese::PCGRandom (SiameseTools.h:80-102)."""
-    M = (1 << 64) - 1
-
-    def __init__(self, y, x=0):
-        self.state, self.inc = 0, ((y << 1) | 1) & self.M
-        self.next()
-        self.state = (self.state + x) & self.M
-        self.next()
-
-    def next(self) -> int:
-        old = self.state
-        self.state = (old * 6364136223846793005 + self.inc) & self.M
-        xs = (((old >> 18) ^ old) >> 27) & 0xFFFFFFFF
-        rot = old >> 59
-        return ((xs >> rot) | (xs << ((-rot) & 31))) & 0xFFFFFFFF
-
-
-def tonk_unit_messages():
-    """TestCompression's stream (TonkUnitTest.cpp:599-700): 100 messages of 400 PCG bytes, seeds
-    0..49 then 50..1 (the second half repeats the first in reverse)."""
-    out = []
-    for i in range(100):
-        seed = 100 - i if i >= 50 else i
-        p = Pcg(seed)
-        out.append(b"".join(p.next().to_bytes(4, "little") for _ in range(100)))
-    return out
-
-
-def mixed_messages(n, seed):
-    """Text-like runs, random bytes and repeats of earlier stretches; lengths 8..MAX."""
-    rng = np.random.default_rng(seed)
-    words = [b"siamese ", b"tonk ", b"packet ", b"recovery ", b"window ", b"lane ", b"sum ", b"ack ", b"0123 "]
-    stream = bytearray()
-    msgs = []
-    for _ in range(n):
-        ln = int(rng.integers(8, MAX + 1))
-        kind = int(rng.integers(0, 4))
-        if kind == 3 and len(stream) > 4000:
-            start = len(stream) - 1 - int(rng.integers(0, min(len(stream) - 1, 40000)))
-            m = bytes(stream[start:start + ln]).ljust(ln, b"x")
-        elif kind == 0:
-            m = rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
-        else:
-            parts = []
-            while sum(map(len, parts)) < ln:
-                parts.append(words[int(rng.integers(0, len(words)))])
-            m = b"".join(parts)[:ln]
-        stream += m
-        msgs.append(m)
-    return msgs
+from conftest import NATIVE, _make
+from lz_streams import (MAX, RefCompressor, RefDecompressor, edge_case_messages, mixed_messages, pack_streams, ref_lib,
+                        run_threads, tonk_unit_messages)
 
 
 # --------------------------------------------------------------------------------------- CPU
@@ -219,13 +119,7 @@ def test_gpu_compress_batch_streams():
     L = ref_lib()
     n_streams, n_msgs = 16, 120
     streams = [mixed_messages(n_msgs, 100 + s) for s in range(n_streams)]
-    stride = max(sum(map(len, s)) for s in streams) + 64
-    host = np.zeros((n_streams, stride), dtype=np.uint8)
-    lens = []
-    for s, ms in enumerate(streams):
-        blob = b"".join(ms)
-        host[s, :len(blob)] = np.frombuffer(blob, dtype=np.uint8)
-        lens += [len(m) for m in ms]
+    host, stride, lens = pack_streams(streams)
     raw, written, ms = compress_batch_host(host.tobytes(), stride, n_streams, n_msgs, lens, MAX, msgs_per_job=8)
     out_h = np.frombuffer(raw, dtype=np.uint8)
     total_in = total_out = 0
@@ -253,23 +147,7 @@ def test_gpu_compressor_edge_cases(max_bytes):
     decompressor."""
     from tonk_amd.compress import MessageCompressor
     L = ref_lib()
-    rng = np.random.default_rng(max_bytes)
-    top = max_bytes
-    msgs = []
-    for k in range(300):
-        kind = k % 6
-        if kind == 0:
-            msgs.append(bytes(rng.integers(0, 256, int(rng.integers(1, 9)), dtype=np.uint8)))
-        elif kind == 1:
-            msgs.append(bytes([k & 0xFF]) * int(rng.integers(9, top + 1)))
-        elif kind == 2:
-            msgs.append((b"abc" * top)[:top])
-        elif kind == 3:
-            msgs.append(bytes(rng.integers(0, 4, top, dtype=np.uint8)))
-        elif kind == 4 and max_bytes > 2048:
-            msgs.append((b"tonk siamese " * 400)[:int(rng.integers(2049, max_bytes + 1))])
-        else:
-            msgs.append(msgs[-1] if msgs else b"x" * 20)
+    msgs = edge_case_messages(max_bytes)
     comp, dec = MessageCompressor(max_bytes), RefDecompressor(L, max_bytes)
     n_comp = 0
     for m in msgs:
@@ -307,13 +185,7 @@ def test_gpu_compress_batch_large_messages(per_job):
                 o = int(rng.integers(0, len(text) - n))
                 ms.append(text[o:o + n])
         streams.append(ms)
-    stride = max(sum(map(len, s)) for s in streams) + 64
-    host = np.zeros((n_streams, stride), dtype=np.uint8)
-    lens = []
-    for s, ms in enumerate(streams):
-        blob = b"".join(ms)
-        host[s, :len(blob)] = np.frombuffer(blob, dtype=np.uint8)
-        lens += [len(m) for m in ms]
+    host, stride, lens = pack_streams(streams)
     raw, written, _ = compress_batch_host(host.tobytes(), stride, n_streams, n_msgs, lens, max_bytes, msgs_per_job=per_job)
     out_h = np.frombuffer(raw, dtype=np.uint8)
     big = 0
@@ -335,28 +207,18 @@ def test_gpu_compressor_concurrent_callers():
     same time (Tonk's connection threads): the calls are combined into shared launches, a leader
     hands leadership on once its own message is done, and every stream is restored in order by
     its own reference decompressor."""
-    import threading
     from tonk_amd.compress import MessageCompressor
     L = ref_lib()
     n_threads, n_msgs = 8, 150
     streams = [mixed_messages(n_msgs, 300 + t) for t in range(n_threads)]
     blocks = [[None] * n_msgs for _ in range(n_threads)]
-    errors = []
 
-    def worker(t):
-        try:
-            comp = MessageCompressor(MAX)
-            for k, m in enumerate(streams[t]):
-                blocks[t][k] = comp.compress(m)
-        except Exception as e:  # (surfaced below)
-            errors.append(repr(e))
+    def worker(t, errors):
+        comp = MessageCompressor(MAX)
+        for k, m in enumerate(streams[t]):
+            blocks[t][k] = comp.compress(m)
 
-    th = [threading.Thread(target=worker, args=(t,)) for t in range(n_threads)]
-    for x in th:
-        x.start()
-    for x in th:
-        x.join(timeout=120)
-    assert not any(x.is_alive() for x in th), "a compressor call did not return"
+    errors = run_threads(n_threads, worker)
     assert not errors, errors
     for t in range(n_threads):
         dec = RefDecompressor(L)

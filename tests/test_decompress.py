@@ -11,145 +11,25 @@ from __future__ import annotations
 
 import ctypes
 import os
-import struct
 import subprocess
-import threading
 
 import numpy as np
 import pytest
 
 from conftest import NATIVE, ROOT, _make
-from test_compress import MAX, RefCompressor, RefDecompressor, mixed_messages, ref_lib, tonk_unit_messages
+from lz_streams import (MAX, Hip, RefCompressor, RefDecompressor, check_batch, edge_case_messages, mixed_messages,
+                        pack_streams, read_cases, ref_lib, ref_slots, rep_offsets, run_threads, skewed, tonk_unit_messages,
+                        write_streams)
 
 STATUS_FAILED = -13  # TAMD_UNLZ_E_FAILED (tonk_amd/csrc/unlz.h)
 
 
-# ------------------------------------------------------------------------------- generators
-
-def mixed_messages_max(n, seed, max_bytes):
-    """test_compress.mixed_messages with the lengths' upper end as a parameter."""
-    rng = np.random.default_rng(seed)
-    words = [b"siamese ", b"tonk ", b"packet ", b"recovery ", b"window ", b"lane ", b"sum ", b"ack ", b"0123 "]
-    stream = bytearray()
-    msgs = []
-    for _ in range(n):
-        ln = int(rng.integers(8, max_bytes + 1))
-        kind = int(rng.integers(0, 4))
-        if kind == 3 and len(stream) > 4000:
-            start = len(stream) - 1 - int(rng.integers(0, min(len(stream) - 1, 40000)))
-            m = bytes(stream[start:start + ln]).ljust(ln, b"x")
-        elif kind == 0:
-            m = rng.integers(0, 256, ln, dtype=np.uint8).tobytes()
-        else:
-            parts = []
-            total = 0
-            while total < ln:
-                parts.append(words[int(rng.integers(0, len(words)))])
-                total += len(parts[-1])
-            m = b"".join(parts)[:ln]
-        stream += m
-        msgs.append(m)
-    return msgs
-
-
-def skewed(n, seed, max_bytes):
-    """Lengths 64..max, bytes drawn from 64 symbols with probability ~ 2^(-i/3)."""
-    rng = np.random.default_rng(seed)
-    p = 2.0 ** (-np.arange(64) / 3.0)
-    p /= p.sum()
-    return [rng.choice(64, size=int(rng.integers(64, max_bytes + 1)), p=p).astype(np.uint8).tobytes() for _ in range(n)]
-
-
-def edge_case_messages(max_bytes):
-    """The list of test_compress.test_gpu_compressor_edge_cases."""
-    rng = np.random.default_rng(max_bytes)
-    top = max_bytes
-    msgs = []
-    for k in range(300):
-        kind = k % 6
-        if kind == 0:
-            msgs.append(bytes(rng.integers(0, 256, int(rng.integers(1, 9)), dtype=np.uint8)))
-        elif kind == 1:
-            msgs.append(bytes([k & 0xFF]) * int(rng.integers(9, top + 1)))
-        elif kind == 2:
-            msgs.append((b"abc" * top)[:top])
-        elif kind == 3:
-            msgs.append(bytes(rng.integers(0, 4, top, dtype=np.uint8)))
-        elif kind == 4 and max_bytes > 2048:
-            msgs.append((b"tonk siamese " * 400)[:int(rng.integers(2049, max_bytes + 1))])
-        else:
-            msgs.append(msgs[-1] if msgs else b"x" * 20)
-    return msgs
-
-
-def rep_offsets(n, seed, max_bytes=MAX):
-    """Records of a fixed stride with a few bytes changed from one to the next: matches separated
-    by short (and no) literal runs at the distances just used, the repeat-offset cases."""
-    rng = np.random.default_rng(seed)
-    msgs = []
-    for _ in range(n):
-        stride = int(rng.integers(24, 90))
-        rec = bytearray(rng.integers(0, 256, stride, dtype=np.uint8).tobytes())
-        m = bytearray()
-        while len(m) < int(rng.integers(300, max_bytes + 1)):
-            kind = int(rng.integers(0, 6))
-            if kind == 0:  # a byte changes
-                rec[int(rng.integers(0, stride))] = int(rng.integers(0, 256))
-                m += rec
-            elif kind == 1:  # a byte is left out: the distance shortens by one
-                cut = int(rng.integers(1, stride - 1))
-                m += rec[:cut] + rec[cut + 1:]
-            elif kind == 2:  # two distances alternate
-                m += rec + rec[:stride // 2]
-            else:
-                m += rec
-        msgs.append(bytes(m[:max_bytes]))
-    return msgs
-
-
 def cpu_streams():
     """(max, messages) of every stream the walk is checked on."""
-    out = [(1300, tonk_unit_messages()), (1300, mixed_messages(300, 5)), (4000, mixed_messages_max(300, 5, 4000)),
-           (24000, mixed_messages_max(48, 5, 24000)), (1300, skewed(120, 9, 1300)), (8000, skewed(40, 9, 8000)),
+    out = [(1300, tonk_unit_messages()), (1300, mixed_messages(300, 5)), (4000, mixed_messages(300, 5, 4000)),
+           (24000, mixed_messages(48, 5, 24000)), (1300, skewed(120, 9, 1300)), (8000, skewed(40, 9, 8000)),
            (1300, rep_offsets(60, 3))]
     out += [(m, edge_case_messages(m)) for m in (1300, 4000, 24000)]
-    return out
-
-
-def write_streams(path, streams):
-    """The stream file of unlz_check: raw messages (is_block 0)."""
-    with open(path, "wb") as f:
-        f.write(b"UNLZ" + struct.pack("<I", len(streams)))
-        for max_bytes, msgs in streams:
-            f.write(struct.pack("<II", max_bytes, len(msgs)))
-            for m in msgs:
-                f.write(struct.pack("<II", 0, len(m)) + m)
-
-
-def read_cases(path, verdicts):
-    """A case file of unlz_check: [(max, [(is_block, bytes, status, restored bytes)])]."""
-    with open(path, "rb") as f:
-        raw = f.read()
-    assert raw[:4] == b"UNLZ"
-    n, = struct.unpack_from("<I", raw, 4)
-    at, out = 8, []
-    for _ in range(n):
-        max_bytes, m = struct.unpack_from("<II", raw, at)
-        at += 8
-        msgs = []
-        for _ in range(m):
-            isb, ln = struct.unpack_from("<II", raw, at)
-            at += 8
-            data = raw[at:at + ln]
-            at += ln
-            status, restored = 0, b""
-            if verdicts:
-                status, r = struct.unpack_from("<iI", raw, at)
-                at += 8
-                restored = raw[at:at + r]
-                at += r
-            msgs.append((bool(isb), data, status, restored))
-        out.append((max_bytes, msgs))
     return out
 
 
@@ -202,6 +82,21 @@ def test_fse_tables_built_by_64_lanes():
     exe = unlz_check()
     r = subprocess.run([exe, "tables"], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-2000:] + r.stderr[-2000:]
+
+
+def test_ring_rule_of_compressor_and_decoder_agree():
+    """The history-ring rule in its two forms, the compressor's linear positions (lz.h RingTrack)
+    and the decoder's ring offset and dictionary length (unlz.h tamd_unlz_place), stepped side by
+    side over 10 maximum sizes x 200 seeded streams x 400 lengths: every position is the running
+    byte count, every message fits the ring, and the compressor's window starts exactly where the
+    decoder's history does.  Restarts and partly overwritten dictionaries both occurred."""
+    exe = unlz_check()
+    r = subprocess.run([exe, "ring"], capture_output=True, text=True, timeout=120)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-2000:] + r.stderr[-2000:]
+    counts = [int(w.rstrip(",")) for w in r.stdout.splitlines()[0].split() if w.rstrip(",").isdigit()]
+    assert len(counts) == 3 and counts[0] == 10 * 200 * 400
+    assert counts[1] > 0 and counts[2] > 0, counts
 
 
 def test_malformed_blocks_under_sanitizers(stream_file, mutant_cases, tmp_path):
@@ -288,32 +183,6 @@ def test_gpu_decompressor_gpu_blocks(which):
     assert n_blocks > 0
 
 
-def ref_slots(L, streams, max_bytes):
-    """Reference-compressed streams in the batch layout: (slots, in_bytes, is_block)."""
-    n_msgs = len(streams[0])
-    slots = np.zeros((len(streams) * n_msgs, max_bytes), dtype=np.uint8)
-    in_bytes, is_block = [], []
-    for s, msgs in enumerate(streams):
-        comp = RefCompressor(L, max_bytes)
-        for k, m in enumerate(msgs):
-            blk = comp.compress(m)
-            data = blk if blk else m
-            slots[s * n_msgs + k, :len(data)] = np.frombuffer(data, dtype=np.uint8)
-            in_bytes.append(len(data))
-            is_block.append(1 if blk else 0)
-    return slots, in_bytes, is_block
-
-
-def check_batch(streams, max_bytes, out, restored, status):
-    n_msgs = len(streams[0])
-    out = np.frombuffer(out, dtype=np.uint8).reshape(-1, max_bytes)
-    for s, msgs in enumerate(streams):
-        for k, m in enumerate(msgs):
-            i = s * n_msgs + k
-            assert status[i] == 0 and restored[i] == len(m), (s, k, status[i], restored[i])
-            assert out[i, :len(m)].tobytes() == m, (s, k)
-
-
 @pytest.mark.gpu
 def test_gpu_decompress_batch_streams():
     """16 streams x 120 messages of the mixed format in one decompress_batch_host call."""
@@ -334,60 +203,13 @@ def test_gpu_decompress_batch_large_messages():
     from tonk_amd.compress import decompress_batch_host
     L = ref_lib()
     max_bytes = 24000
-    streams = [mixed_messages_max(24, 5, max_bytes), mixed_messages_max(24, 6, max_bytes),
+    streams = [mixed_messages(24, 5, max_bytes), mixed_messages(24, 6, max_bytes),
                skewed(24, 9, max_bytes), skewed(24, 10, max_bytes)]
     slots, in_bytes, is_block = ref_slots(L, streams, max_bytes)
     types = {int(slots[i, 0]) & 3 for i in range(len(in_bytes)) if is_block[i]}
     assert {2, 3} <= types, types  # Compressed and Treeless literals are in the input
     out, restored, status, _ = decompress_batch_host(slots.tobytes(), 4, 24, in_bytes, is_block, max_bytes)
     check_batch(streams, max_bytes, out, restored, status)
-
-
-class Hip:
-    """Device memory through the HIP runtime the library itself uses (the one mapped into this
-    process with it), for the tests that hand device pointers to the batch calls."""
-
-    def __init__(self):
-        import tonk_amd
-        tonk_amd.lib()
-        # (the library binds to the runtime already in the process when torch brought one first,
-        # else to the system's: the copy outside torch is the library's own whenever there is one)
-        with open("/proc/self/maps") as f:
-            paths = sorted({ln.split()[-1] for ln in f if "libamdhip64" in ln}, key=lambda p: "/torch/" in p)
-        path = paths[0]
-        L = self.L = ctypes.CDLL(path)
-        vp, sz = ctypes.c_void_p, ctypes.c_size_t
-        L.hipMalloc.argtypes = [ctypes.POINTER(vp), sz]
-        L.hipFree.argtypes = [vp]
-        L.hipMemcpy.argtypes = [vp, vp, sz, ctypes.c_int]
-        L.hipMemset.argtypes = [vp, ctypes.c_int, sz]
-        L.hipDeviceSynchronize.argtypes = []
-        self.owned = []
-
-    def malloc(self, n, fill=0):
-        p = ctypes.c_void_p()
-        assert self.L.hipMalloc(ctypes.byref(p), n) == 0
-        self.owned.append(p.value)
-        assert self.L.hipMemset(p.value, fill, n) == 0
-        return p.value
-
-    def upload(self, ptr, arr):
-        arr = np.ascontiguousarray(arr, dtype=np.uint8)
-        assert self.L.hipMemcpy(ptr, arr.ctypes.data, arr.size, 1) == 0  # hipMemcpyHostToDevice
-
-    def download(self, ptr, n):
-        out = np.empty(n, dtype=np.uint8)
-        assert self.L.hipMemcpy(out.ctypes.data, ptr, n, 2) == 0  # hipMemcpyDeviceToHost
-        return out
-
-    def copy(self, dst, src, n):
-        assert self.L.hipMemcpy(dst, src, n, 3) == 0  # hipMemcpyDeviceToDevice
-
-    def close(self):
-        self.L.hipDeviceSynchronize()
-        for p in self.owned:
-            self.L.hipFree(p)
-        self.owned = []
 
 
 @pytest.mark.gpu
@@ -401,13 +223,7 @@ def test_gpu_compress_then_decompress_on_device():
     hip = Hip()
     n_streams, n_msgs = 8, 60
     streams = [mixed_messages(n_msgs, 200 + s) for s in range(n_streams)]
-    stride = max(sum(map(len, s)) for s in streams) + 64
-    host = np.zeros((n_streams, stride), dtype=np.uint8)
-    lens = []
-    for s, ms in enumerate(streams):
-        blob = b"".join(ms)
-        host[s, :len(blob)] = np.frombuffer(blob, dtype=np.uint8)
-        lens += [len(m) for m in ms]
+    host, stride, lens = pack_streams(streams)
     total = n_streams * n_msgs
     d_in = hip.malloc(host.size)
     hip.upload(d_in, host.reshape(-1))
@@ -472,13 +288,7 @@ def test_gpu_chain_on_torch_tensors(tmp_path):
     import sys
     n_streams, n_msgs = 8, 60
     streams = [mixed_messages(n_msgs, 200 + s) for s in range(n_streams)]
-    stride = max(sum(map(len, s)) for s in streams) + 64
-    host = np.zeros((n_streams, stride), dtype=np.uint8)
-    lens = []
-    for s, ms in enumerate(streams):
-        blob = b"".join(ms)
-        host[s, :len(blob)] = np.frombuffer(blob, dtype=np.uint8)
-        lens += [len(m) for m in ms]
+    host, stride, lens = pack_streams(streams)
     path = str(tmp_path / "chain")
     np.savez(path + ".in.npz", host=host, lens=np.asarray(lens, dtype=np.uint32))
     r = subprocess.run([sys.executable, "-c", TORCH_CHAIN, ROOT, path, str(MAX)], capture_output=True, text=True,
@@ -639,28 +449,78 @@ def test_gpu_decompressor_concurrent_callers():
     from tonk_amd.compress import MessageCompressor, MessageDecompressor
     n_threads, n_msgs = 8, 150
     streams = [mixed_messages(n_msgs, 300 + t) for t in range(n_threads)]
-    errors = []
 
-    def worker(t):
-        try:
-            comp, dec = MessageCompressor(MAX), MessageDecompressor(MAX)
-            for k, m in enumerate(streams[t]):
-                blk = comp.compress(m)
-                if blk:
-                    if dec.decompress(blk) != m:
-                        errors.append((t, k))
-                        return
-                else:
-                    dec.insert_uncompressed(m)
-            comp.close()
-            dec.close()
-        except Exception as e:  # (surfaced below)
-            errors.append(repr(e))
+    def worker(t, errors):
+        comp, dec = MessageCompressor(MAX), MessageDecompressor(MAX)
+        for k, m in enumerate(streams[t]):
+            blk = comp.compress(m)
+            if blk:
+                if dec.decompress(blk) != m:
+                    errors.append((t, k))
+                    return
+            else:
+                dec.insert_uncompressed(m)
+        comp.close()
+        dec.close()
 
-    th = [threading.Thread(target=worker, args=(t,)) for t in range(n_threads)]
-    for x in th:
-        x.start()
-    for x in th:
-        x.join(timeout=120)
-    assert not any(x.is_alive() for x in th), "a call did not return"
+    errors = run_threads(n_threads, worker)
     assert not errors, errors
+
+
+@pytest.mark.gpu
+def test_gpu_recycled_device_memory():
+    """The device memory of a closed compressor and decompressor goes to the next ones, stale
+    bytes included (lz_host.h DevicePool); at 24,000 the messages go through the scratch path.
+    First generation: a stream through a compressor-decompressor pair, the reference decompressor
+    beside it; both closed.  Second generation: a block of the first stream whose match reaches
+    into history, given as the first block to a new decompressor, fails or restores exactly what
+    the reference restores from a fresh state: the old history is not visible.  That block has a
+    decompressor of its own, since a rejected block leaves a decompressor failed for good and an
+    accepted one would put bytes into the history that the new compressor does not have.  Then a
+    different stream through a new pair: every message restored.  Once at 1300 with 40 messages
+    a stream, once at 24,000 with 12."""
+    L = ref_lib()
+    for max_bytes, first, second in ((1300, (40, 7), (40, 8)), (24000, (12, 5), (12, 6))):
+        _two_generations(L, max_bytes, first, second)
+
+
+def _two_generations(L, max_bytes, first, second):
+    from tonk_amd.compress import MessageCompressor, MessageDecompressor, _lib
+
+    def generation(msgs):
+        comp, dec, rdec = MessageCompressor(max_bytes), MessageDecompressor(max_bytes), RefDecompressor(L, max_bytes)
+        blocks = []
+        for k, m in enumerate(msgs):
+            blk = comp.compress(m)
+            assert rdec.feed(blk, m) == m, k
+            if blk:
+                assert dec.decompress(blk) == m, k
+            else:
+                dec.insert_uncompressed(m)
+            blocks.append(blk)
+        comp.close()
+        dec.close()
+        return blocks
+
+    msgs = mixed_messages(first[0], first[1], max_bytes)
+    blocks = generation(msgs)
+    assert any(blocks)
+
+    # what a fresh reference decompressor makes of each block alone: the first one it rejects or
+    # restores differently from the message reaches into history
+    def fresh_reference(blk):
+        return RefDecompressor(L, max_bytes).decompress(blk)
+
+    stale = next(k for k, b in enumerate(blocks) if k and b and fresh_reference(b) != msgs[k])
+    want = fresh_reference(blocks[stale])
+    dec = MessageDecompressor(max_bytes)
+    dest = ctypes.create_string_buffer(max_bytes)
+    got = ctypes.c_uint(0)
+    rc = _lib().tamd_decompressor_decompress(dec._h, blocks[stale], len(blocks[stale]), dest, max_bytes, ctypes.byref(got))
+    print(f"block {stale} of the first stream on a fresh decompressor: rc {rc}, reference "
+          f"{'rejects' if want is None else 'restores %d bytes' % len(want)}")
+    assert rc < 0 or (rc == 0 and want is not None and dest.raw[:got.value] == want)
+    dec.close()
+
+    blocks = generation(mixed_messages(second[0], second[1], max_bytes))
+    assert any(blocks)

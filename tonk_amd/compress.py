@@ -18,6 +18,8 @@ import ctypes
 from . import lib as _lib_loader
 
 _bound = False
+_u32p, _i32p, _u8p = ctypes.POINTER(ctypes.c_uint32), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
+_uintp, _f32p = ctypes.POINTER(ctypes.c_uint), ctypes.POINTER(ctypes.c_float)
 
 
 def _lib() -> ctypes.CDLL:
@@ -25,45 +27,54 @@ def _lib() -> ctypes.CDLL:
     L = _lib_loader()
     if not _bound:
         vp, u32, u64 = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64
-        L.tamd_compressor_create.restype = vp
-        L.tamd_compressor_create.argtypes = [ctypes.c_uint]
+        for create, destroy in ((L.tamd_compressor_create, L.tamd_compressor_destroy),
+                                (L.tamd_decompressor_create, L.tamd_decompressor_destroy)):
+            create.restype = vp
+            create.argtypes = [ctypes.c_uint]
+            destroy.restype = None
+            destroy.argtypes = [vp]
         L.tamd_compressor_compress.restype = ctypes.c_int
-        L.tamd_compressor_compress.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p,
-                                               ctypes.POINTER(ctypes.c_uint)]
-        L.tamd_compressor_destroy.restype = None
-        L.tamd_compressor_destroy.argtypes = [vp]
-        L.tamd_compress_batch.restype = ctypes.c_int
-        L.tamd_compress_batch.argtypes = [vp, u64, u32, u32, ctypes.POINTER(u32), u32, vp, ctypes.POINTER(u32), u32,
-                                          ctypes.POINTER(ctypes.c_float)]
-        L.tamd_compress_batch_host.restype = ctypes.c_int
-        L.tamd_compress_batch_host.argtypes = [vp, u64, u32, u32, ctypes.POINTER(u32), u32, vp, ctypes.POINTER(u32),
-                                               u32, ctypes.POINTER(ctypes.c_float)]
-        i32p, u8p = ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_uint8)
-        L.tamd_decompressor_create.restype = vp
-        L.tamd_decompressor_create.argtypes = [ctypes.c_uint]
+        L.tamd_compressor_compress.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint, vp, _uintp]
+        for f in (L.tamd_compress_batch, L.tamd_compress_batch_host):
+            f.restype = ctypes.c_int
+            f.argtypes = [vp, u64, u32, u32, _u32p, u32, vp, _u32p, u32, _f32p]
         L.tamd_decompressor_insert_uncompressed.restype = None
         L.tamd_decompressor_insert_uncompressed.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint]
         L.tamd_decompressor_decompress.restype = ctypes.c_int
-        L.tamd_decompressor_decompress.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint, ctypes.c_void_p, ctypes.c_uint,
-                                                   ctypes.POINTER(ctypes.c_uint)]
-        L.tamd_decompressor_destroy.restype = None
-        L.tamd_decompressor_destroy.argtypes = [vp]
+        L.tamd_decompressor_decompress.argtypes = [vp, ctypes.c_char_p, ctypes.c_uint, vp, ctypes.c_uint, _uintp]
         for f in (L.tamd_decompress_batch, L.tamd_decompress_batch_host):
             f.restype = ctypes.c_int
-            f.argtypes = [vp, u32, u32, ctypes.POINTER(u32), u8p, u32, vp, ctypes.POINTER(u32), i32p,
-                          ctypes.POINTER(ctypes.c_float)]
+            f.argtypes = [vp, u32, u32, _u32p, _u8p, u32, vp, _u32p, _i32p, _f32p]
         _bound = True
     return L
 
 
-class MessageCompressor:
-    """tonk::MessageCompressor on the GPU.  Raises when no gfx950 device is usable."""
+class _Handle:
+    """A compressor or decompressor of the library: created or RuntimeError, destroyed once."""
+    _create = _destroy = ""  # the library's calls
+    _h = None
 
     def __init__(self, max_compressed_message_bytes: int):
         self.max = int(max_compressed_message_bytes)
-        self._h = _lib().tamd_compressor_create(self.max)
+        self._h = getattr(_lib(), self._create)(self.max)
         if not self._h:
-            raise RuntimeError("tonk_amd: tamd_compressor_create failed (no gfx950 device, or bad size)")
+            raise RuntimeError(f"tonk_amd: {self._create} failed (no gfx950 device, or bad size)")
+
+    def close(self) -> None:
+        if self._h:
+            getattr(_lib(), self._destroy)(self._h)
+            self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+class MessageCompressor(_Handle):
+    """tonk::MessageCompressor on the GPU.  Raises when no gfx950 device is usable."""
+    _create, _destroy = "tamd_compressor_create", "tamd_compressor_destroy"
+
+    def __init__(self, max_compressed_message_bytes: int):
+        super().__init__(max_compressed_message_bytes)
         self._dest = ctypes.create_string_buffer(self.max + 64)
 
     def compress(self, message: bytes) -> bytes:
@@ -72,14 +83,6 @@ class MessageCompressor:
         if rc != 0:
             raise RuntimeError(f"tonk_amd: compress failed (rc={rc})")
         return self._dest.raw[:w.value]
-
-    def close(self) -> None:
-        if self._h:
-            _lib().tamd_compressor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
 
 def compress_batch(dev_data: int, stride: int, n_streams: int, n_msgs: int, lens, max_bytes: int, dev_out: int,
@@ -93,9 +96,8 @@ def compress_batch(dev_data: int, stride: int, n_streams: int, n_msgs: int, lens
     L = np.ascontiguousarray(lens, dtype=np.uint32)
     W = np.zeros(total, dtype=np.uint32)
     ms = ctypes.c_float(0.0)
-    u32p = ctypes.POINTER(ctypes.c_uint32)
-    rc = _lib().tamd_compress_batch(dev_data, stride, n_streams, n_msgs, L.ctypes.data_as(u32p), max_bytes, dev_out,
-                                    W.ctypes.data_as(u32p), msgs_per_job, ctypes.byref(ms))
+    rc = _lib().tamd_compress_batch(dev_data, stride, n_streams, n_msgs, L.ctypes.data_as(_u32p), max_bytes, dev_out,
+                                    W.ctypes.data_as(_u32p), msgs_per_job, ctypes.byref(ms))
     if rc != 0:
         raise RuntimeError(f"tonk_amd: compress_batch failed (rc={rc})")
     return W, ms.value
@@ -118,15 +120,13 @@ def compress_batch_host(data, stride: int, n_streams: int, n_msgs: int, lens, ma
     return out.raw, list(W), ms.value
 
 
-class MessageDecompressor:
+class MessageDecompressor(_Handle):
     """tonk::MessageDecompressor on the GPU.  Raises when no gfx950 device is usable; after a
     block fails to decode every later call raises too (the reference's connection closes)."""
+    _create, _destroy = "tamd_decompressor_create", "tamd_decompressor_destroy"
 
     def __init__(self, max_compressed_message_bytes: int):
-        self.max = int(max_compressed_message_bytes)
-        self._h = _lib().tamd_decompressor_create(self.max)
-        if not self._h:
-            raise RuntimeError("tonk_amd: tamd_decompressor_create failed (no gfx950 device, or bad size)")
+        super().__init__(max_compressed_message_bytes)
         self._dest = ctypes.create_string_buffer(self.max)
 
     def decompress(self, block: bytes) -> bytes:
@@ -138,14 +138,6 @@ class MessageDecompressor:
 
     def insert_uncompressed(self, message: bytes) -> None:
         _lib().tamd_decompressor_insert_uncompressed(self._h, message, len(message))
-
-    def close(self) -> None:
-        if self._h:
-            _lib().tamd_decompressor_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        self.close()
 
 
 def decompress_batch(dev_in: int, n_streams: int, n_msgs: int, in_bytes, is_block, max_bytes: int, dev_out: int):
@@ -162,10 +154,8 @@ def decompress_batch(dev_in: int, n_streams: int, n_msgs: int, in_bytes, is_bloc
     R = np.zeros(total, dtype=np.uint32)
     S = np.zeros(total, dtype=np.int32)
     ms = ctypes.c_float(0.0)
-    rc = _lib().tamd_decompress_batch(dev_in, n_streams, n_msgs, N.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                      B.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), max_bytes, dev_out,
-                                      R.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                      S.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), ctypes.byref(ms))
+    rc = _lib().tamd_decompress_batch(dev_in, n_streams, n_msgs, N.ctypes.data_as(_u32p), B.ctypes.data_as(_u8p),
+                                      max_bytes, dev_out, R.ctypes.data_as(_u32p), S.ctypes.data_as(_i32p), ctypes.byref(ms))
     if rc != 0:
         raise RuntimeError(f"tonk_amd: decompress_batch failed (rc={rc})")
     return R, S, ms.value

@@ -4,6 +4,7 @@
 #include "../../include/tonk_compress.h"
 #include "combine.h"
 #include "lz.h"
+#include "lz_host.h"
 
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -16,15 +17,10 @@
 
 extern "C" __global__ void tamd_lz_compress(const tamd_lz_job*, uint32_t, const tamd_lz_msg*, const uint8_t*,
                                             uint8_t*, uint32_t*, uint8_t*, unsigned long long*);
-// (lz.hip: two jobs per 128-thread workgroup)
-static const uint32_t kLzJobsPerGroup = TAMD_LZ_WAVES;
 extern "C" __global__ void tamd_lz_scatter_ring(const tamd_lz_scatter*, const uint8_t*);
 
 namespace tamd {
 namespace {
-
-// History ring of PacketCompression.h:36-63 (kCompressionDictBytes = 24 * 1000).
-const uint32_t kDictBytes = 24 * 1000;
 
 // The FSE table blob on each device (uploaded once per device, kept for the process).
 struct DeviceTables {
@@ -52,50 +48,17 @@ const uint8_t* device_fse(int device) {
     return d;
 }
 
-bool device_ok() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return false;
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
+// tamd_lz_compress with a wave per job (TAMD_LZ_WAVES jobs per workgroup); e0 / e1: events around it
+void launch(hipStream_t st, hipEvent_t e0, hipEvent_t e1, const tamd_lz_job* jobs, uint32_t n_jobs,
+            const tamd_lz_msg* msgs, const uint8_t* fse, uint8_t* out, uint32_t* written, uint8_t* scratch,
+            unsigned long long* prof) {
+    const dim3 grid((n_jobs + TAMD_LZ_WAVES - 1) / TAMD_LZ_WAVES), block(64 * TAMD_LZ_WAVES);
+    if (e0)
+        hipExtLaunchKernelGGL(tamd_lz_compress, grid, block, 0, st, e0, e1, 0, jobs, n_jobs, msgs, fse, out, written,
+                              scratch, prof);
+    else
+        hipLaunchKernelGGL(tamd_lz_compress, grid, block, 0, st, jobs, n_jobs, msgs, fse, out, written, scratch, prof);
 }
-
-// MessageCompressor's ring (PacketCompression.h:44-63 Allocate/Commit, used by Compress at
-// PacketCompression.cpp:79-83 and identically by the decompressor): every message is placed at
-// the write offset unless `max` bytes would not fit, in which case the ring restarts at 0 and a
-// new contiguous segment begins.  In linear stream positions, the decompressor decoding a message
-// holds the current segment before it and, as zstd's external dictionary, the previous segment's
-// bytes that the current segment has not overwritten yet (ring offsets past the message's end).
-struct RingTrack {
-    uint32_t max = 0, next = 0;  // ring write offset
-    uint64_t lin = 0;            // linear position of the next message
-    uint64_t seg = 0;            // linear start of the current segment
-    uint64_t prev = 0;           // linear start of the previous segment (seg when none)
-    bool have_prev = false;
-    // place a message of n bytes; returns its linear position and window start
-    void place(uint32_t n, uint64_t* pos, uint64_t* win) {
-        if (next + max > kDictBytes) {
-            if (next != 0) {
-                prev = seg;
-                have_prev = true;
-                seg = lin;
-            }
-            next = 0;
-        }
-        *pos = lin;
-        if (have_prev) {
-            // previous segment bytes at ring offsets >= next + n are still intact
-            const uint64_t w = prev + next + n;
-            *win = w < seg ? w : seg;
-        } else {
-            *win = seg;
-        }
-        next += n;
-        lin += n;
-    }
-};
 
 }  // namespace
 
@@ -125,63 +88,21 @@ struct LzRequest : CombineRequest<Compressor> {
 Combiner<LzRequest> g_combiner;
 
 // leader-only launch state (grown on demand)
-struct LzBatchState {
-    int device = -1;
-    hipStream_t st = nullptr;
-    uint8_t* h_in = nullptr;   // pinned: scatter descs | msgs | jobs | message bytes
-    uint8_t* d_in = nullptr;
-    size_t in_cap = 0;
-    uint8_t* h_out = nullptr;  // pinned: written[] | compressed blocks
-    uint8_t* d_out = nullptr;
-    size_t out_cap = 0;
-    uint8_t* d_scratch = nullptr;  // messages above TAMD_LZ_MAX_MESSAGE
-    size_t scratch_cap = 0;
+struct LzBatchState : LeaderStream {
+    Buffer in;       // pinned + device: scatter descs | msgs | jobs | message bytes
+    Buffer out;      // pinned + device: written[] | compressed blocks
+    Buffer scratch;  // device: messages above TAMD_LZ_MAX_MESSAGE
 } g_batch;
 
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// Device rings of destroyed compressors are kept for the next ones: hipFree waits for the whole
-// device (every stream of the process, the Siamese codecs' too), and Tonk destroys a compressor
-// with every connection it closes.
-std::mutex g_ring_mu;
-std::vector<std::pair<int, uint8_t*>> g_free_rings;  // (device, ring)
-uint8_t* take_ring(int device) {
-    std::lock_guard<std::mutex> g(g_ring_mu);
-    for (size_t i = 0; i < g_free_rings.size(); ++i)
-        if (g_free_rings[i].first == device) {
-            uint8_t* r = g_free_rings[i].second;
-            g_free_rings[i] = g_free_rings.back();
-            g_free_rings.pop_back();
-            return r;
-        }
-    return nullptr;
-}
-
-bool grow(uint8_t*& h, uint8_t*& d, size_t& cap, size_t need) {
-    if (need <= cap) return true;
-    if (h) hipHostFree(h);
-    if (d) hipFree(d);
-    h = d = nullptr;
-    cap = need + need / 2;
-    if (hipHostMalloc((void**)&h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc((void**)&d, cap) != hipSuccess) {
-        cap = 0;
-        return false;
-    }
-    return true;
-}
+// Device rings of destroyed compressors, kept for the next ones (lz_host.h).
+DevicePool<TAMD_LZ_RING + TAMD_LZ_MIRROR> g_rings;
 
 // Runs one batch (leader, no lock held); every request of `b` belongs to device b[0]->c->device
 // and names a distinct compressor.
 void run_batch(const std::vector<LzRequest*>& in) {
     LzBatchState& S = g_batch;
     const int dev = in[0]->c->device;
-    bool ok = hipSetDevice(dev) == hipSuccess;
-    if (ok && S.device != dev) {  // (a process compresses on one device in practice)
-        if (S.st) hipStreamDestroy(S.st);
-        S.st = nullptr;
-        ok = hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking) == hipSuccess;
-        S.device = ok ? dev : -1;
-    }
+    bool ok = S.use(dev);
     const uint8_t* fse = ok ? device_fse(dev) : nullptr;
     ok = ok && fse;
     // A compressor whose device ring cannot be allocated fails on its own (rc -2, sticky) and is
@@ -190,9 +111,8 @@ void run_batch(const std::vector<LzRequest*>& in) {
     live.reserve(in.size());
     for (LzRequest* r : in) {
         if (ok && !r->c->ring && !r->c->failed) {
-            uint8_t* ring = take_ring(dev);
-            if (!ring && hipMalloc((void**)&ring, TAMD_LZ_RING + TAMD_LZ_MIRROR) != hipSuccess) r->c->failed = true;
-            else r->c->ring = ring;
+            r->c->ring = g_rings.take(dev);
+            if (!r->c->ring) r->c->failed = true;
         }
         if (ok && r->c->ring && !r->c->failed) {
             live.push_back(r);
@@ -214,21 +134,13 @@ void run_batch(const std::vector<LzRequest*>& in) {
     const size_t o_jobs = o_msgs + align16(n * sizeof(tamd_lz_msg));
     const size_t o_data = o_jobs + align16(n * sizeof(tamd_lz_job));
     const size_t o_blocks = align16(n * 4);
-    ok = ok && grow(S.h_in, S.d_in, S.in_cap, o_data + data_bytes) && grow(S.h_out, S.d_out, S.out_cap, o_blocks + out_bytes);
-    if (ok && scratch_bytes > S.scratch_cap) {
-        if (S.d_scratch) hipFree(S.d_scratch);
-        S.d_scratch = nullptr;
-        S.scratch_cap = scratch_bytes + scratch_bytes / 2;
-        if (hipMalloc((void**)&S.d_scratch, S.scratch_cap) != hipSuccess) {
-            S.scratch_cap = 0;
-            ok = false;
-        }
-    }
+    ok = ok && S.in.grow(o_data + data_bytes, true) && S.out.grow(o_blocks + out_bytes, true) &&
+         S.scratch.grow(scratch_bytes, false);
     if (ok) {
         size_t scr = 0;
-        tamd_lz_scatter* sc = (tamd_lz_scatter*)S.h_in;
-        tamd_lz_msg* ms = (tamd_lz_msg*)(S.h_in + o_msgs);
-        tamd_lz_job* jb = (tamd_lz_job*)(S.h_in + o_jobs);
+        tamd_lz_scatter* sc = (tamd_lz_scatter*)S.in.h;
+        tamd_lz_msg* ms = (tamd_lz_msg*)(S.in.h + o_msgs);
+        tamd_lz_job* jb = (tamd_lz_job*)(S.in.h + o_jobs);
         size_t din = 0, dout = o_blocks;
         for (size_t i = 0; i < n; ++i) {
             LzRequest* r = b[i];
@@ -238,7 +150,7 @@ void run_batch(const std::vector<LzRequest*>& in) {
             // positions are rebased to a multiple of the ring size below the window (same ring
             // slots, small numbers)
             const uint64_t base = win & ~(uint64_t)(TAMD_LZ_RING - 1);
-            memcpy(S.h_in + o_data + din, r->data, r->bytes);
+            memcpy(S.in.h + o_data + din, r->data, r->bytes);
             sc[i].ring = c->ring;
             sc[i].slot = (uint32_t)(pos & (TAMD_LZ_RING - 1));
             sc[i].bytes = r->bytes;
@@ -263,29 +175,27 @@ void run_batch(const std::vector<LzRequest*>& in) {
             din += align16(r->bytes);
             dout += align16(c->max);
         }
-        ok = hipMemcpyAsync(S.d_in, S.h_in, o_data + data_bytes, hipMemcpyHostToDevice, S.st) == hipSuccess;
+        ok = hipMemcpyAsync(S.in.d, S.in.h, o_data + data_bytes, hipMemcpyHostToDevice, S.st) == hipSuccess;
         if (ok) {
             hipLaunchKernelGGL(tamd_lz_scatter_ring, dim3((uint32_t)n), dim3(256), 0, S.st,
-                               (const tamd_lz_scatter*)S.d_in, (const uint8_t*)(S.d_in + o_data));
-            hipLaunchKernelGGL(tamd_lz_compress, dim3((uint32_t)((n + kLzJobsPerGroup - 1) / kLzJobsPerGroup)),
-                               dim3(64 * kLzJobsPerGroup), 0, S.st, (const tamd_lz_job*)(S.d_in + o_jobs), (uint32_t)n,
-                               (const tamd_lz_msg*)(S.d_in + o_msgs), fse, S.d_out + o_blocks, (uint32_t*)S.d_out,
-                               S.d_scratch, (unsigned long long*)nullptr);
+                               (const tamd_lz_scatter*)S.in.d, (const uint8_t*)(S.in.d + o_data));
+            launch(S.st, nullptr, nullptr, (const tamd_lz_job*)(S.in.d + o_jobs), (uint32_t)n,
+                   (const tamd_lz_msg*)(S.in.d + o_msgs), fse, S.out.d + o_blocks, (uint32_t*)S.out.d, S.scratch.d, nullptr);
             ok = hipGetLastError() == hipSuccess;
         }
-        ok = ok && hipMemcpyAsync(S.h_out, S.d_out, o_blocks + out_bytes, hipMemcpyDeviceToHost, S.st) == hipSuccess;
+        ok = ok && hipMemcpyAsync(S.out.h, S.out.d, o_blocks + out_bytes, hipMemcpyDeviceToHost, S.st) == hipSuccess;
         ok = ok && hipStreamSynchronize(S.st) == hipSuccess;
     }
     size_t dout = o_blocks;
     for (size_t i = 0; i < n; ++i) {
         LzRequest* r = b[i];
         Compressor* c = r->c;
-        const uint32_t w = ok ? ((const uint32_t*)S.h_out)[i] : 0;
+        const uint32_t w = ok ? ((const uint32_t*)S.out.h)[i] : 0;
         if (!ok || c->failed || w > c->max) {
             c->failed = true;
             r->rc = -2;
         } else {
-            if (w) memcpy(r->dest, S.h_out + dout, w);
+            if (w) memcpy(r->dest, S.out.h + dout, w);
             *r->written = w;
             r->rc = 0;
         }
@@ -295,7 +205,7 @@ void run_batch(const std::vector<LzRequest*>& in) {
 }  // namespace
 
 extern "C" void* tamd_compressor_create(unsigned max_bytes) {
-    if (max_bytes == 0 || max_bytes + max_bytes > TAMD_LZ_RING || max_bytes > kDictBytes) return nullptr;
+    if (max_bytes == 0 || max_bytes + max_bytes > TAMD_LZ_RING || max_bytes > TAMD_LZ_DICT) return nullptr;
     if (!device_ok()) return nullptr;
     Compressor* c = new Compressor();
     c->max = max_bytes;
@@ -308,10 +218,7 @@ extern "C" void tamd_compressor_destroy(void* cp) {
     Compressor* c = (Compressor*)cp;
     if (!c) return;
     g_combiner.wait_idle(c);  // (no call of this compressor is queued or in flight)
-    if (c->ring) {  // (no launch reads it any more: its last call was waited for)
-        std::lock_guard<std::mutex> g(g_ring_mu);
-        g_free_rings.push_back(std::make_pair(c->device, c->ring));
-    }
+    if (c->ring) g_rings.put(c->device, c->ring);  // (no launch reads it any more: its last call was waited for)
     delete c;
 }
 
@@ -334,7 +241,7 @@ extern "C" int tamd_compress_batch(const void* dev_data, uint64_t stride, uint32
                                    const uint32_t* lens, uint32_t max_bytes, void* dev_out, uint32_t* written_host,
                                    uint32_t msgs_per_job, float* kernel_ms) {
     if (!dev_data || !lens || !dev_out || !written_host || !n_streams || !n_msgs || !max_bytes ||
-        max_bytes > kDictBytes)
+        max_bytes > TAMD_LZ_DICT)
         return -1;
     if (stride > 0xffffffffull) return -1;  // linear positions are 32-bit per stream
     int dev = 0;
@@ -393,54 +300,26 @@ extern "C" int tamd_compress_batch(const void* dev_data, uint64_t stride, uint32
     // persistent launch state (grown on demand): stream, descriptor and result buffers, events
     static std::mutex mu;
     static hipStream_t st = nullptr;
-    static tamd_lz_job* d_jobs = nullptr;
-    static tamd_lz_msg* d_msgs = nullptr;
-    static uint32_t* d_written = nullptr;
-    static size_t cap_jobs = 0, cap_msgs = 0;
     static hipEvent_t e0 = nullptr, e1 = nullptr;
-    static uint8_t* d_scratch = nullptr;
-    static size_t cap_scratch = 0;
+    // (d_msgs and d_written are sized in entries, `total` each: they grow together)
+    static Buffer scratch, d_jobs, d_msgs, d_written;
     std::lock_guard<std::mutex> g(mu);
-    bool ok = true;
-    if (scratch_bytes > cap_scratch) {
-        if (d_scratch) hipFree(d_scratch);
-        d_scratch = nullptr;
-        cap_scratch = scratch_bytes + scratch_bytes / 2;
-        ok = hipMalloc((void**)&d_scratch, cap_scratch) == hipSuccess;
-        if (!ok) cap_scratch = 0;
-    }
+    bool ok = scratch.grow(scratch_bytes, false);
     if (ok && !st) ok = hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess &&
                   hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-    if (ok && jobs.size() > cap_jobs) {
-        if (d_jobs) hipFree(d_jobs);
-        d_jobs = nullptr;
-        cap_jobs = jobs.size() + jobs.size() / 2;
-        ok = hipMalloc((void**)&d_jobs, cap_jobs * sizeof(tamd_lz_job)) == hipSuccess;
-        if (!ok) cap_jobs = 0;
-    }
-    if (ok && total > cap_msgs) {
-        if (d_msgs) hipFree(d_msgs);
-        if (d_written) hipFree(d_written);
-        d_msgs = nullptr;
-        d_written = nullptr;
-        cap_msgs = total + total / 2;
-        ok = hipMalloc((void**)&d_msgs, cap_msgs * sizeof(tamd_lz_msg)) == hipSuccess &&
-             hipMalloc((void**)&d_written, cap_msgs * 4) == hipSuccess;
-        if (!ok) cap_msgs = 0;
-    }
-    ok = ok && hipMemcpyAsync(d_jobs, jobs.data(), jobs.size() * sizeof(tamd_lz_job), hipMemcpyHostToDevice, st) ==
+    ok = ok && d_jobs.grow(jobs.size(), false, sizeof(tamd_lz_job)) && d_msgs.grow(total, false, sizeof(tamd_lz_msg)) &&
+         d_written.grow(total, false, 4);
+    ok = ok && hipMemcpyAsync(d_jobs.d, jobs.data(), jobs.size() * sizeof(tamd_lz_job), hipMemcpyHostToDevice, st) ==
                    hipSuccess;
-    ok = ok && hipMemcpyAsync(d_msgs, msgs.data(), total * sizeof(tamd_lz_msg), hipMemcpyHostToDevice, st) ==
+    ok = ok && hipMemcpyAsync(d_msgs.d, msgs.data(), total * sizeof(tamd_lz_msg), hipMemcpyHostToDevice, st) ==
                    hipSuccess;
     // profiling only: TONK_AMD_LZ_PROF=1 prints the phase totals of the launch (lz.hip LZ_PHASE)
     static const bool prof_on = getenv("TONK_AMD_LZ_PROF") != nullptr;
     unsigned long long* d_prof = nullptr;
     if (ok && prof_on) ok = hipMalloc((void**)&d_prof, jobs.size() * TAMD_LZ_PHASES * 8) == hipSuccess;
     if (ok) {
-        const uint32_t nj = (uint32_t)jobs.size();
-        hipExtLaunchKernelGGL(tamd_lz_compress, dim3((nj + kLzJobsPerGroup - 1) / kLzJobsPerGroup),
-                              dim3(64 * kLzJobsPerGroup), 0, st, e0, e1, 0, d_jobs, nj, d_msgs, fse, (uint8_t*)dev_out,
-                              d_written, d_scratch, d_prof);
+        launch(st, e0, e1, (const tamd_lz_job*)d_jobs.d, (uint32_t)jobs.size(), (const tamd_lz_msg*)d_msgs.d, fse,
+               (uint8_t*)dev_out, (uint32_t*)d_written.d, scratch.d, d_prof);
         ok = hipGetLastError() == hipSuccess;
     }
     if (ok && d_prof) {
@@ -456,7 +335,7 @@ extern "C" int tamd_compress_batch(const void* dev_data, uint64_t stride, uint32
                 t[3] / q, t[4] / q, t[7] / (double)jobs.size());
         hipFree(d_prof);
     }
-    ok = ok && hipMemcpyAsync(written_host, d_written, total * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
+    ok = ok && hipMemcpyAsync(written_host, d_written.d, total * 4, hipMemcpyDeviceToHost, st) == hipSuccess;
     ok = ok && hipStreamSynchronize(st) == hipSuccess;
     if (ok && kernel_ms) {
         float ms = 0;

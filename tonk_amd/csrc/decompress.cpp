@@ -3,6 +3,7 @@
 // launches of tamd_lz_decompress (unlz.hip).  The block reader itself is unlz.h.
 #include "../../include/tonk_compress.h"
 #include "combine.h"
+#include "lz_host.h"
 #include "unlz.h"
 
 #include <hip/hip_runtime.h>
@@ -17,38 +18,6 @@ extern "C" __global__ void tamd_lz_decompress(const tamd_unlz_job*, uint32_t, co
 
 namespace tamd {
 namespace {
-
-bool device_ok() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 1) return false;
-    int dev = 0;
-    hipGetDevice(&dev);
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return false;
-    return strncmp(prop.gcnArchName, "gfx950", 6) == 0;
-}
-
-size_t align16(size_t n) { return (n + 15) & ~(size_t)15; }
-
-// A device buffer (and, when asked, a pinned host twin) grown on demand; contents are not kept.
-struct Buffer {
-    uint8_t* h = nullptr;
-    uint8_t* d = nullptr;
-    size_t cap = 0;
-    bool grow(size_t need, bool host) {
-        if (need <= cap) return true;
-        if (h) hipHostFree(h);
-        if (d) hipFree(d);
-        h = d = nullptr;
-        cap = need + need / 2;
-        if (hipMalloc((void**)&d, cap) != hipSuccess ||
-            (host && hipHostMalloc((void**)&h, cap, hipHostMallocDefault) != hipSuccess)) {
-            cap = 0;
-            return false;
-        }
-        return true;
-    }
-};
 
 void launch(hipStream_t st, hipEvent_t e0, hipEvent_t e1, const tamd_unlz_job* jobs, uint32_t n_jobs,
             const tamd_unlz_msg* msgs, const uint8_t* in, uint8_t* out, uint8_t* scratch, uint32_t* restored,
@@ -94,49 +63,25 @@ struct UnlzRequest : CombineRequest<Decompressor> {
 Combiner<UnlzRequest> g_combiner;
 
 // leader-only launch state
-struct UnlzBatchState {
-    int device = -1;
-    hipStream_t st = nullptr;
+struct UnlzBatchState : LeaderStream {
     Buffer in, out, scratch;  // in: jobs | msgs | bytes; out: restored[] | status[] | block outputs
 } g_batch;
 
-// Stream memory of destroyed decompressors is kept for the next ones (hipFree waits for the
-// whole device, and Tonk destroys a decompressor with every connection it closes).
-std::mutex g_stream_mu;
-std::vector<std::pair<int, uint8_t*>> g_free_streams;
-uint8_t* take_stream(int device) {
-    std::lock_guard<std::mutex> g(g_stream_mu);
-    for (size_t i = 0; i < g_free_streams.size(); ++i)
-        if (g_free_streams[i].first == device) {
-            uint8_t* r = g_free_streams[i].second;
-            g_free_streams[i] = g_free_streams.back();
-            g_free_streams.pop_back();
-            return r;
-        }
-    return nullptr;
-}
+// Stream memory of destroyed decompressors, kept for the next ones (lz_host.h).
+DevicePool<TAMD_UNLZ_STREAM_BYTES> g_streams;
 
 // Runs one batch (leader, no lock held): per request one job = the decompressor's queued
 // uncompressed messages in order, then its block.
 void run_batch(const std::vector<UnlzRequest*>& b) {
     UnlzBatchState& S = g_batch;
     const int dev = b[0]->c->device;
-    bool ok = hipSetDevice(dev) == hipSuccess;
-    if (ok && S.device != dev) {
-        if (S.st) hipStreamDestroy(S.st);
-        S.st = nullptr;
-        ok = hipStreamCreateWithFlags(&S.st, hipStreamNonBlocking) == hipSuccess;
-        S.device = ok ? dev : -1;
-    }
+    bool ok = S.use(dev);
     size_t n_msgs = 0, in_bytes = 0, out_bytes = 0, scratch_bytes = 0;
     for (UnlzRequest* r : b) {
         Decompressor* c = r->c;
         if (ok && !c->stream && !c->failed) {
-            c->stream = take_stream(dev);
-            if (!c->stream && hipMalloc((void**)&c->stream, TAMD_UNLZ_STREAM_BYTES) != hipSuccess) {
-                c->stream = nullptr;
-                c->failed = true;
-            }
+            c->stream = g_streams.take(dev);
+            if (!c->stream) c->failed = true;
         }
         n_msgs += c->q_lens.size() + (r->block ? 1 : 0);
         in_bytes += align16(c->q_bytes.size()) + align16(r->bytes);
@@ -254,10 +199,7 @@ extern "C" void tamd_decompressor_destroy(void* dp) {
     Decompressor* c = (Decompressor*)dp;
     if (!c) return;
     g_combiner.wait_idle(c);
-    if (c->stream) {
-        std::lock_guard<std::mutex> g(g_stream_mu);
-        g_free_streams.push_back(std::make_pair(c->device, c->stream));
-    }
+    if (c->stream) g_streams.put(c->device, c->stream);
     delete c;
 }
 

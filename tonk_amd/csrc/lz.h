@@ -14,6 +14,44 @@
 #define TAMD_LZ_RING 65536u        // per-compressor device ring of the stream's bytes (the drop-in)
 #define TAMD_LZ_MIRROR 64u         // the ring's first bytes repeated after it (wide loads at its end)
 #define TAMD_LZ_PHASES 8u          // (profiling: 100 MHz ticks per job and phase, TONK_AMD_LZ_PROF)
+#define TAMD_LZ_DICT 24000u        // history ring of both sides: kCompressionDictBytes (PacketCompression.h:40)
+
+// The history-ring rule, host only (compress.cpp and the check programs of tests/native; the
+// decoder keeps the same rule as ring offset and dictionary length: unlz.h tamd_unlz_place).
+// MessageCompressor's ring (PacketCompression.h:44-63 Allocate/Commit, used by Compress at
+// PacketCompression.cpp:79-83 and identically by the decompressor): every message is placed at
+// the write offset unless `max` bytes would not fit, in which case the ring restarts at 0 and a
+// new contiguous segment begins.  In linear stream positions, the decompressor decoding a message
+// holds the current segment before it and, as zstd's external dictionary, the previous segment's
+// bytes that the current segment has not overwritten yet (ring offsets past the message's end).
+struct RingTrack {
+    uint32_t max = 0, next = 0;  // ring write offset
+    uint64_t lin = 0;            // linear position of the next message
+    uint64_t seg = 0;            // linear start of the current segment
+    uint64_t prev = 0;           // linear start of the previous segment (seg when none)
+    bool have_prev = false;
+    // place a message of n bytes; returns its linear position and window start
+    void place(uint32_t n, uint64_t* pos, uint64_t* win) {
+        if (next + max > TAMD_LZ_DICT) {
+            if (next != 0) {
+                prev = seg;
+                have_prev = true;
+                seg = lin;
+            }
+            next = 0;
+        }
+        *pos = lin;
+        if (have_prev) {
+            // previous segment bytes at ring offsets >= next + n are still intact
+            const uint64_t w = prev + next + n;
+            *win = w < seg ? w : seg;
+        } else {
+            *win = seg;
+        }
+        next += n;
+        lin += n;
+    }
+};
 
 // The drop-in's staging: message bytes land in their compressor's ring (one workgroup each).
 typedef struct tamd_lz_scatter {

@@ -33,7 +33,7 @@ enum {
     TAMD_CNT_N
 };
 
-#define TAMD_UNLZ_RING 24000u   // kCompressionDictBytes (PacketCompression.h:40)
+#define TAMD_UNLZ_RING TAMD_LZ_DICT  // kCompressionDictBytes (lz.h)
 #define TAMD_UNLZ_HUF_LOG 11u   // largest Huffman table log (RFC 8878 s4.2.1)
 #define TAMD_UNLZ_LL_LOG 9u
 #define TAMD_UNLZ_ML_LOG 9u

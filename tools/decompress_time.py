@@ -19,7 +19,6 @@ import ctypes
 import json
 import os
 import statistics
-import struct
 import subprocess
 import sys
 import tempfile
@@ -28,15 +27,13 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-MAX = 1300
+sys.path.insert(0, os.path.join(ROOT, "oracle"))
+import msgcodec_py  # noqa: E402
+from msgcodec_py import MAX  # noqa: E402
 
 
 def ref_compress_all(data, lens, n_streams, n_msgs):
-    L = ctypes.CDLL(os.path.join(ROOT, "oracle", "_ref", "libmsgcodec_ref.so"))
-    L.ref_comp_new.restype = ctypes.c_void_p
-    L.ref_comp_new.argtypes = [ctypes.c_uint]
-    L.ref_comp.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint)]
-    L.ref_comp_free.argtypes = [ctypes.c_void_p]
+    L = msgcodec_py.load()
     slots = np.zeros((n_streams * n_msgs, MAX), dtype=np.uint8)
     written = np.zeros(n_streams * n_msgs, dtype=np.uint32)
     w = ctypes.c_uint(0)
@@ -64,16 +61,6 @@ def fill_uncompressed(slots, written, data, lens, n_streams, n_msgs):
             if written[i] == 0:
                 slots[i, :n] = data[s, pos:pos + n]
             pos += n
-
-
-def write_blocks(path, slots, in_bytes, is_block, n_streams, n_msgs):
-    with open(path, "wb") as f:
-        f.write(b"UNLZ" + struct.pack("<I", n_streams))
-        for s in range(n_streams):
-            f.write(struct.pack("<II", MAX, n_msgs))
-            for k in range(n_msgs):
-                i = s * n_msgs + k
-                f.write(struct.pack("<II", int(is_block[i]), int(in_bytes[i])) + slots[i, :in_bytes[i]].tobytes())
 
 
 def main():
@@ -148,7 +135,8 @@ def main():
             continue
         with tempfile.TemporaryDirectory() as td:
             path = os.path.join(td, "blocks.bin")
-            write_blocks(path, slots, in_bytes, is_block, n_streams, n_msgs)
+            msgcodec_py.write_streams(path, [(MAX, [(is_block[i], slots[i, :in_bytes[i]].tobytes())
+                                                    for i in range(s * n_msgs, (s + 1) * n_msgs)]) for s in range(n_streams)])
             r = subprocess.run([exe, "bench", path, str(a.threads), "9"], capture_output=True, text=True, check=True)
         cpu = json.loads(r.stdout.strip().splitlines()[-1])
         result["cases"][name] = {
