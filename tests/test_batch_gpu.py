@@ -1,0 +1,434 @@
+"""The batched codecs over the caller's device packets (include/tonk_batch.h, tonk_amd.BatchCodec)
+on an MI355X against the reference codec (oracle/_ref/libsiamese_ref.so) driven through ctypes with
+the same calls in the same per-stream order: packet numbers, result codes, recovery packets,
+acknowledgements and recovered payloads must be equal.  Every caller buffer has 64 guard bytes of
+0xA5 on each side, checked after every call."""
+from __future__ import annotations
+
+import os
+
+import numpy as np
+import pytest
+
+from batch_ref import (DISABLED, DUPLICATE, INVALID, LENGTHS, NEED_MORE, REF, SUCCESS, Guarded, RefDecoder, RefEncoder,
+                       slots)
+from lz_streams import Hip
+
+pytestmark = [pytest.mark.gpu,
+              pytest.mark.skipif(not os.path.exists(REF), reason="reference codec not built (oracle/Makefile)")]
+
+MAXB = 4000
+OVER = 11  # TAMD_BATCH_RECOVERY_OVERHEAD
+LENS18 = LENGTHS[:18]
+N_STREAMS, N_ORIG, PER_CALL = 3, 72, 9
+ENCODE_LIST = [0, 1, 1, 2]  # every stream, stream 1 twice
+
+
+def stream_lengths(s):
+    rot = LENS18[s % 18:] + LENS18[:s % 18]
+    return (rot * 4)[:N_ORIG]
+
+
+def make_payloads(n_streams, lengths_of, seed):
+    rng = np.random.default_rng(seed)
+    return [[rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in lengths_of(s)] for s in range(n_streams)]
+
+
+@pytest.fixture(scope="module")
+def hip():
+    h = Hip()
+    yield h
+    h.close()
+
+
+@pytest.fixture(scope="module")
+def payloads():
+    return make_payloads(N_STREAMS, stream_lengths, 7)
+
+
+@pytest.fixture(scope="module")
+def ref_traffic(payloads):
+    """The reference encoders' traffic for the three streams, computed once: per round and
+    stream the recovery packets of ENCODE_LIST, then six more per stream at the end."""
+    encs = [RefEncoder() for _ in range(N_STREAMS)]
+    rounds = []
+    for r in range(N_ORIG // PER_CALL):
+        for s in range(N_STREAMS):
+            for k in range(PER_CALL):
+                rc, pn = encs[s].add(payloads[s][r * PER_CALL + k])
+                assert rc == 0 and pn == r * PER_CALL + k
+        recs = []
+        for s in ENCODE_LIST:
+            rc, data = encs[s].encode()
+            assert rc == 0
+            recs.append((s, data))
+        rounds.append(recs)
+    tail = []
+    for k in range(6):
+        for s in range(N_STREAMS):
+            rc, data = encs[s].encode()
+            assert rc == 0
+            tail.append((s, data))
+    rounds.append(tail)
+    for e in encs:
+        e.close()
+    return rounds
+
+
+def new_codec(n_streams=N_STREAMS, maxb=MAXB, arena=96 << 20):
+    import tonk_amd
+    return tonk_amd.BatchCodec(n_streams, maxb, arena)
+
+
+def check_all(*bufs):
+    for b in bufs:
+        b.check()
+
+
+def recovery_slots(out, pitch, nbytes):
+    """Recovery packets of an encode's output buffer; bytes past each packet must keep the fill."""
+    raw = out.download()
+    got = []
+    for i, n in enumerate(nbytes):
+        slot = raw[i * pitch:(i + 1) * pitch]
+        assert (slot[n:] == Guarded.FILL).all(), f"slot {i} written past its {n} bytes"
+        got.append(slot[:n].tobytes())
+    return got
+
+
+@pytest.mark.parametrize("pitch,skew", [(4001, 0), (4096, 0), (4001, 5)])
+def test_encoder_matches_reference(hip, payloads, pitch, skew):
+    out_pitch = pitch + OVER if pitch == 4001 else pitch  # 4012 (odd slots) / 4096
+    bc = new_codec()
+    refs = [RefEncoder() for _ in range(N_STREAMS)]
+    ref_dec = [RefDecoder() for _ in range(N_STREAMS)]
+    src = Guarded(hip, N_STREAMS * PER_CALL * pitch, skew)
+    out = Guarded(hip, len(ENCODE_LIST) * out_pitch, skew)
+    try:
+        # nothing added yet: NeedMoreData on both
+        out.fill()
+        nb, rc = bc.encode(ENCODE_LIST, out.ptr, out_pitch)
+        assert [r.encode()[0] for r in (refs[0], refs[1], refs[1], refs[2])] == [NEED_MORE] * 4
+        assert list(rc) == [NEED_MORE] * 4 and list(nb) == [0] * 4
+        check_all(src, out)
+        assert (out.download() == Guarded.FILL).all()
+        for r in range(N_ORIG // PER_CALL):
+            # the call's packets, streams interleaved (list order inside a stream is the add order)
+            stream = [s for k in range(PER_CALL) for s in range(N_STREAMS)]
+            index = [r * PER_CALL + k for k in range(PER_CALL) for s in range(N_STREAMS)]
+            pk = [payloads[s][i] for s, i in zip(stream, index)]
+            src.upload(slots(pk, pitch))
+            pn, rc = bc.encoder_add(stream, [len(p) for p in pk], src.ptr, pitch)
+            want = [refs[s].add(p) for s, p in zip(stream, pk)]
+            assert list(rc) == [w[0] for w in want] and list(pn) == [w[1] for w in want]
+            check_all(src, out)
+            out.fill()
+            nb, rc = bc.encode(ENCODE_LIST, out.ptr, out_pitch)
+            want = [refs[s].encode() for s in ENCODE_LIST]
+            assert list(rc) == [w[0] for w in want], r
+            assert list(nb) == [len(w[1]) for w in want], r
+            got = recovery_slots(out, out_pitch, nb)
+            for i, (g, w) in enumerate(zip(got, want)):
+                assert g == w[1], f"round {r} recovery packet {i} (stream {ENCODE_LIST[i]}) differs"
+            check_all(src, out)
+            for s, w in zip(ENCODE_LIST, want):
+                assert ref_dec[s].add_recovery(w[1]) == 0
+            for s in range(N_STREAMS):
+                for k in range(PER_CALL):
+                    i = r * PER_CALL + k
+                    if i not in (5, 20):
+                        assert ref_dec[s].add_original(i, payloads[s][i]) == 0
+            if r == 3:  # after the fourth add call: the receivers' acknowledgements
+                for s in range(N_STREAMS):
+                    arc, ack = ref_dec[s].ack()
+                    assert arc == 0 and ack
+                    assert bc.encoder_ack(s, ack) == refs[s].ack(ack)
+    finally:
+        bc.close()
+        for x in refs + ref_dec:
+            x.close()
+
+
+def test_encode_of_a_single_packet(hip):
+    """A stream holding one packet gets the single-packet row; its neighbour holds nothing."""
+    bc = new_codec(2, 1300, 16 << 20)
+    ref = RefEncoder()
+    src, out = Guarded(hip, 1300), Guarded(hip, 2 * 1311, 3)
+    try:
+        data = bytes(range(256)) * 5 + b"xyz"
+        src.upload(slots([data[:1283]], 1300))
+        pn, rc = bc.encoder_add([0], [1283], src.ptr, 1300)
+        assert (list(pn), list(rc)) == ([0], [0]) and ref.add(data[:1283]) == (0, 0)
+        out.fill()
+        nb, rc = bc.encode([0, 1], out.ptr, 1311)
+        want = ref.encode()
+        assert list(rc) == [want[0], NEED_MORE] and list(nb) == [len(want[1]), 0]
+        assert recovery_slots(out, 1311, nb)[0] == want[1]
+        check_all(src, out)
+    finally:
+        bc.close()
+        ref.close()
+
+
+def lost_original(i):
+    return i % 11 == 3 or 40 <= i <= 44
+
+
+def decode_and_compare(bc, ref_dec, out, pitch, cap, tag):
+    out.fill()
+    rc, o_s, o_n, o_b = bc.decode(list(range(len(ref_dec))), out.ptr, pitch, cap)
+    want = [d.decode_if_ready() for d in ref_dec]
+    assert list(rc) == [w[0] for w in want], tag
+    flat = [(s, num, data) for s, w in enumerate(want) for num, data in w[1]]
+    assert list(o_s) == [f[0] for f in flat] and list(o_n) == [f[1] for f in flat], tag
+    assert list(o_b) == [len(f[2]) for f in flat], tag
+    raw = out.download()
+    for j, f in enumerate(flat):
+        slot = raw[j * pitch:(j + 1) * pitch]
+        assert slot[:len(f[2])].tobytes() == f[2], f"{tag}: recovered packet {f[1]} of stream {f[0]} differs"
+        assert (slot[len(f[2]):] == Guarded.FILL).all(), f"{tag}: slot {j} written past its payload"
+    assert (raw[len(flat) * pitch:] == Guarded.FILL).all(), tag
+    out.check()
+    return flat
+
+
+@pytest.mark.parametrize("pitch", [4001, 4096])
+def test_decoder_matches_reference(hip, payloads, ref_traffic, pitch):
+    rec_pitch = pitch + OVER if pitch == 4001 else pitch
+    bc = new_codec()
+    ref_dec = [RefDecoder() for _ in range(N_STREAMS)]
+    src = Guarded(hip, N_STREAMS * PER_CALL * pitch, 1)
+    rec = Guarded(hip, 18 * rec_pitch, 2)
+    out = Guarded(hip, 32 * pitch, 7)
+    recovered = 0
+    try:
+        for r, recs in enumerate(ref_traffic):
+            if r < N_ORIG // PER_CALL:
+                ent = [(s, r * PER_CALL + k) for k in range(PER_CALL) for s in range(N_STREAMS)
+                       if not lost_original(r * PER_CALL + k)]
+                pk = [payloads[s][i] for s, i in ent]
+                src.upload(slots(pk, pitch))
+                rc = bc.decoder_add_original([e[0] for e in ent], [e[1] for e in ent], [len(p) for p in pk], src.ptr, pitch)
+                assert list(rc) == [ref_dec[s].add_original(i, p) for (s, i), p in zip(ent, pk)]
+                check_all(src, rec, out)
+                recovered += len(decode_and_compare(bc, ref_dec, out, pitch, 32, f"round {r} originals"))
+            rec.upload(slots([d for _, d in recs], rec_pitch))
+            rc = bc.decoder_add_recovery([s for s, _ in recs], [len(d) for _, d in recs], rec.ptr, rec_pitch)
+            assert list(rc) == [ref_dec[s].add_recovery(d) for s, d in recs], r
+            check_all(src, rec, out)
+            recovered += len(decode_and_compare(bc, ref_dec, out, pitch, 32, f"round {r} recovery"))
+            for s in range(N_STREAMS):
+                assert bc.decoder_ack(s) == ref_dec[s].ack(), (r, s)
+        assert recovered >= 20  # (the losses are mostly recovered: the comparison is not vacuous)
+    finally:
+        bc.close()
+        for x in ref_dec:
+            x.close()
+
+
+def test_round_trip_on_the_device(hip):
+    """16 streams x 192 originals through both sides of one handle: the encode output buffer is the
+    add_recovery input (lost entries get 0 bytes and are skipped with rc 1), 3 % seeded loss on
+    originals and recovery packets alike, acknowledgements every second tick.  The reference codec,
+    driven on the CPU with the same calls and deliveries, says what must be recovered."""
+    n_streams, n_orig, tick, n_rec, pitch = 16, 192, 16, 2, 1311
+    rng = np.random.default_rng(99)
+    odd_lens = rng.integers(1, 1301, (n_streams, n_orig))
+    pay = make_payloads(n_streams, lambda s: [1300] * n_orig if s % 2 == 0 else list(odd_lens[s]), 5)
+    lost_o = rng.random((n_streams, n_orig)) < 0.03
+    lost_r = rng.random((n_streams, n_orig // tick * n_rec)) < 0.03
+    bc = new_codec(n_streams, 1300, 256 << 20)
+    r_enc = [RefEncoder() for _ in range(n_streams)]
+    r_dec = [RefDecoder() for _ in range(n_streams)]
+    src = Guarded(hip, n_streams * tick * pitch, 9)
+    rec = Guarded(hip, n_streams * n_rec * pitch, 1)
+    out = Guarded(hip, 64 * pitch, 0)
+    want_all, got_all = [], []
+    try:
+        for t in range(n_orig // tick):
+            ent = [(s, t * tick + k) for s in range(n_streams) for k in range(tick)]
+            pk = [pay[s][i] for s, i in ent]
+            src.upload(slots(pk, pitch))
+            streams, lens = [e[0] for e in ent], [len(p) for p in pk]
+            pn, rc = bc.encoder_add(streams, lens, src.ptr, pitch)
+            assert list(rc) == [0] * len(ent) and list(pn) == [e[1] for e in ent]
+            for (s, i), p in zip(ent, pk):
+                assert r_enc[s].add(p) == (0, i)
+            # the same buffer into the receivers, lost originals skipped
+            dl = [0 if lost_o[s, i] else n for (s, i), n in zip(ent, lens)]
+            rc = bc.decoder_add_original(streams, [e[1] for e in ent], dl, src.ptr, pitch)
+            assert list(rc) == [INVALID if n == 0 else SUCCESS for n in dl]
+            for (s, i), p, n in zip(ent, pk, dl):
+                if n:
+                    assert r_dec[s].add_original(i, p) == 0
+            elist = [s for s in range(n_streams) for _ in range(n_rec)]
+            rec.fill()
+            nb, rc = bc.encode(elist, rec.ptr, pitch)
+            assert list(rc) == [0] * len(elist)
+            rl = [0 if lost_r[s, t * n_rec + (j % n_rec)] else int(n) for j, (s, n) in enumerate(zip(elist, nb))]
+            rc = bc.decoder_add_recovery(elist, rl, rec.ptr, pitch)
+            ref_rc = []
+            for s, n in zip(elist, rl):
+                erc, data = r_enc[s].encode()
+                assert erc == 0
+                ref_rc.append(r_dec[s].add_recovery(data) if n else INVALID)
+            assert list(rc) == ref_rc, t
+            out.fill()
+            rc, o_s, o_n, o_b = bc.decode(list(range(n_streams)), out.ptr, pitch, 64)
+            raw = out.download()
+            for j in range(len(o_s)):
+                got_all.append((t, int(o_s[j]), int(o_n[j]), raw[j * pitch:j * pitch + int(o_b[j])].tobytes()))
+            for s in range(n_streams):
+                wrc, wp = r_dec[s].decode_if_ready()
+                assert rc[s] == wrc, (t, s)
+                want_all += [(t, s, num, data) for num, data in wp]
+            check_all(src, rec, out)
+            if t % 2 == 1:
+                for s in range(n_streams):
+                    arc, ack = bc.decoder_ack(s)
+                    assert (arc, ack) == r_dec[s].ack()
+                    assert bc.encoder_ack(s, ack) == r_enc[s].ack(ack)
+        assert got_all == want_all
+        assert len(want_all) >= 30 and all(d == pay[s][num] for _, s, num, d in want_all)
+    finally:
+        bc.close()
+        for x in r_enc + r_dec:
+            x.close()
+
+
+def test_refusals(hip):
+    import tonk_amd
+    pitch = 1311
+    bc = new_codec(2, 1300, 32 << 20)
+    refs = [RefEncoder(), RefEncoder()]
+    ref_dec = RefDecoder()
+    rng = np.random.default_rng(3)
+    pk = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (700, 700, 700, 1300, 33, 700, 700, 700)]
+    src, out = Guarded(hip, 8 * pitch, 3), Guarded(hip, 8 * pitch, 0)
+    try:
+        src.upload(slots(pk, pitch))
+        # len 0 and len = max + 1 between good neighbours of the same stretch
+        lens = [700, 0, 700, 1301, 33, 700, 700, 700]
+        pn, rc = bc.encoder_add([0] * 8, lens, src.ptr, pitch)
+        assert list(rc) == [0, INVALID, 0, INVALID, 0, 0, 0, 0]
+        good = [i for i in range(8) if rc[i] == 0]
+        assert [int(pn[i]) for i in good] == list(range(6))
+        for i in good:
+            assert refs[0].add(pk[i])[0] == 0
+        # refused as a whole, nothing changed: a stream id out of range, a pitch below the largest len
+        with pytest.raises(RuntimeError, match="stream id out of range"):
+            bc.encoder_add([0, 2], [700, 700], src.ptr, pitch)
+        with pytest.raises(RuntimeError, match="pitch"):
+            bc.encoder_add([0, 0], [700, 1300], src.ptr, 1299)
+        with pytest.raises(RuntimeError, match="pitch"):
+            bc.encode([0], out.ptr, 1310)
+        with pytest.raises(RuntimeError, match="stream id out of range"):
+            bc.encode([0, 7], out.ptr, pitch)
+        check_all(src, out)
+        out.fill()
+        nb, rc = bc.encode([0, 0], out.ptr, pitch)
+        want = [refs[0].encode(), refs[0].encode()]
+        assert list(rc) == [0, 0] and recovery_slots(out, pitch, nb) == [w[1] for w in want]
+        # a duplicate original; the receiver lacks originals 1 and 3 (pk[2] and pk[5]); nums -> their index in pk
+        nums = [0, 2, 4, 5, 0]
+        idx = [0, 4, 6, 7, 0]
+        src.upload(slots([pk[i] for i in idx], pitch))
+        rc = bc.decoder_add_original([1] * 5, nums, [len(pk[i]) for i in idx], src.ptr, pitch)
+        assert list(rc) == [0, 0, 0, 0, DUPLICATE]
+        assert [ref_dec.add_original(n, pk[i]) for n, i in zip(nums, idx)] == [0, 0, 0, 0, DUPLICATE]
+        # two recovery packets recover two losses: cap 1 leaves the stream for the next call
+        src.upload(slots([w[1] for w in want], pitch))
+        rc = bc.decoder_add_recovery([1, 1], [len(w[1]) for w in want], src.ptr, pitch)
+        assert list(rc) == [ref_dec.add_recovery(w[1]) for w in want] == [0, 0]
+        out.fill()
+        rc, o_s, o_n, o_b = bc.decode([0, 1], out.ptr, pitch, 1)
+        assert list(rc) == [NEED_MORE, NEED_MORE] and len(o_s) == 0
+        assert (out.download() == Guarded.FILL).all()
+        rc, o_s, o_n, o_b = bc.decode([0, 1], out.ptr, pitch, 2)
+        wrc, wp = ref_dec.decode_if_ready()
+        assert list(rc) == [NEED_MORE, wrc] and wrc == 0
+        assert [(int(n), int(b)) for n, b in zip(o_n, o_b)] == [(n, len(d)) for n, d in wp] == [(1, 700), (3, 700)]
+        raw = out.download()
+        for j, (n, d) in enumerate(wp):
+            assert raw[j * pitch:j * pitch + len(d)].tobytes() == d
+        with pytest.raises(RuntimeError, match="pitch"):
+            bc.decode([1], out.ptr, 1299, 4)
+        check_all(src, out)
+        assert isinstance(bc, tonk_amd.BatchCodec)
+    finally:
+        bc.close()
+        for x in refs + [ref_dec]:
+            x.close()
+
+
+@pytest.mark.parametrize("length", [100, 1300])
+def test_damaged_recovery_packet(hip, length):
+    """Byte 0 of stream 1's recovery packet is XORed with 0xFF on its way to both decoders: the
+    recovered row's length header is wrong (length 100: it announces more than the row holds, the
+    kernel's bounds check; 1300: a shorter packet of garbage).  Whatever the reference returns is
+    expected; streams 0 and 2 of the same calls recover their packet."""
+    pitch = length + OVER
+    bc = new_codec(3, length, 32 << 20)
+    encs = [RefEncoder() for _ in range(3)]
+    decs = [RefDecoder() for _ in range(3)]
+    pay = make_payloads(3, lambda s: [length] * 10, 11)
+    src, out = Guarded(hip, 27 * pitch, 5), Guarded(hip, 8 * pitch, 6)
+    try:
+        recs = []
+        for s in range(3):
+            for p in pay[s]:
+                assert encs[s].add(p)[0] == 0
+            rc, data = encs[s].encode()
+            assert rc == 0
+            if s == 1:
+                data = bytes([data[0] ^ 0xFF]) + data[1:]
+            recs.append(data)
+        ent = [(s, i) for s in range(3) for i in range(10) if i != 4]
+        src.upload(slots([pay[s][i] for s, i in ent], pitch))
+        rc = bc.decoder_add_original([e[0] for e in ent], [e[1] for e in ent], [length] * len(ent), src.ptr, pitch)
+        assert list(rc) == [decs[s].add_original(i, pay[s][i]) for s, i in ent] == [0] * len(ent)
+        src.upload(slots(recs, pitch))
+        rc = bc.decoder_add_recovery([0, 1, 2], [len(d) for d in recs], src.ptr, pitch)
+        assert list(rc) == [decs[s].add_recovery(recs[s]) for s in range(3)]
+        check_all(src, out)
+        flat = decode_and_compare(bc, decs, out, pitch, 8, f"damaged, length {length}")
+        assert [f[:2] for f in flat if f[0] != 1] == [(0, 4), (2, 4)]
+        assert all(f[2] == pay[f[0]][4] for f in flat if f[0] != 1)
+        check_all(src, out)
+        # afterwards the three streams answer as the reference's do
+        assert [bc.decoder_ack(s)[0] for s in range(3)] == [decs[s].ack()[0] for s in range(3)]
+    finally:
+        bc.close()
+        for x in encs + decs:
+            x.close()
+
+
+def test_full_arena_disables_one_stream(hip):
+    """A stream whose share of the arena is full is disabled (result 5 for the packets that did not
+    fit and for every later call on it), as a codec of the C ABI is; its neighbour goes on and still
+    equals the reference."""
+    share = 88 << 10  # 65 rows of a 1300-byte original
+    bc = new_codec(2, 1300, 2 * share)
+    ref = RefEncoder()
+    rng = np.random.default_rng(17)
+    pk = [rng.integers(0, 256, 1300, dtype=np.uint8).tobytes() for _ in range(64)]
+    src, out = Guarded(hip, 64 * 1300, 1), Guarded(hip, 2 * 1311, 2)
+    try:
+        src.upload(slots(pk, 1300))
+        pn, rc = bc.encoder_add([0] * 64, [1300] * 64, src.ptr, 1300)
+        assert list(rc) == [SUCCESS] * 64 and list(pn) == list(range(64))
+        pn, rc = bc.encoder_add([0] * 64, [1300] * 64, src.ptr, 1300)
+        assert list(rc) == [DISABLED] * 64
+        pn, rc = bc.encoder_add([0, 1, 0, 1], [1300] * 4, src.ptr, 1300)
+        assert list(rc) == [DISABLED, SUCCESS, DISABLED, SUCCESS] and [int(pn[1]), int(pn[3])] == [0, 1]
+        assert ref.add(pk[1]) == (0, 0) and ref.add(pk[3]) == (0, 1)
+        out.fill()
+        nb, rc = bc.encode([0, 1], out.ptr, 1311)
+        want = ref.encode()
+        assert list(rc) == [DISABLED, want[0]] and list(nb) == [0, len(want[1])]
+        raw = out.download()
+        assert (raw[:1311] == Guarded.FILL).all() and raw[1311:1311 + nb[1]].tobytes() == want[1]
+        check_all(src, out)
+    finally:
+        bc.close()
+        ref.close()

@@ -267,3 +267,9 @@ class Session:
             self.close()
         except Exception:
             pass
+
+
+# Batched encoders and decoders over the caller's own device packets (include/tonk_batch.h).
+from .batch import BatchCodec  # noqa: E402
+
+__all__.append("BatchCodec")

@@ -46,6 +46,9 @@ public:
                          uint32_t header_bytes, uint32_t payload_bytes, bool borrowed,
                          uint64_t layout = 0);
     Result is_ready();
+    // After is_ready() succeeded: the most packets the next decode() can return (a caller with
+    // bounded room for them, batch.cpp).
+    uint32_t ready_count() const { return has_recovered_ ? (uint32_t)recovered_.size() : cr_.lost_count; }
     // siamese_decode: recovered packets are appended to `out` (increasing packet number).
     Result decode(std::vector<RecoveredPacket*>& out);
     // `recovered_now`: a packet the decode just returned, looked up even when that decode disabled

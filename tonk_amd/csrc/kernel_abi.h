@@ -1,5 +1,5 @@
 // kernel_abi.h -- the records the helper kernels of kernels.hip read and write, and the
-// prototypes of every kernel the host launches (device.cpp, server.cpp): one definition for both
+// prototypes of every kernel the host launches (device.cpp, server.cpp, batch.cpp): one definition for both
 // sides.  The records are plain C; the prototypes need a HIP translation unit.
 #pragma once
 #include <stdint.h>
@@ -20,6 +20,15 @@ typedef struct DigestDesc { uint32_t row, skip, len, pad; } DigestDesc;
 /* tamd_verify_rows: mode 0 a recovery packet of `len` bytes, 1 a recovered original */
 typedef struct VerifyDesc { uint32_t row, len, mode, pad; } VerifyDesc;
 typedef struct VerifyOut { uint64_t hash; uint32_t len, ok; } VerifyOut;
+/* tamd_frame_rows (frame.hip): the caller's device address of the packet, arena row (64-B units),
+   packet bytes, row capacity (a multiple of 64), raw != 0: no length header (a recovery packet) */
+typedef struct FrameDesc { uint64_t src; uint32_t row, len, cap, raw; } FrameDesc;
+/* tamd_unframe_rows: the caller's slot, arena row, the bytes the row may hold (its length header is
+   checked against them); raw != 0: `upper` bytes are copied as they are (a recovery packet) */
+typedef struct UnframeDesc { uint64_t dst; uint32_t row, upper, raw, pad; } UnframeDesc;
+typedef struct UnframeOut { uint32_t len, status; } UnframeOut;  /* payload bytes, TAMD_FRAME_* (frame.h) */
+/* tamd_gather_tails: the caller's device address of a packet and its bytes; 8 bytes out each */
+typedef struct TailDesc { uint64_t src; uint32_t total, pad; } TailDesc;
 
 static_assert(sizeof(GenDesc) == 24, "GenDesc");
 static_assert(sizeof(GatherDesc) == 12, "GatherDesc");
@@ -28,6 +37,10 @@ static_assert(sizeof(HostCopyDesc) == 16, "HostCopyDesc");
 static_assert(sizeof(DigestDesc) == 16, "DigestDesc");
 static_assert(sizeof(VerifyDesc) == 16, "VerifyDesc");
 static_assert(sizeof(VerifyOut) == 16, "VerifyOut");
+static_assert(sizeof(FrameDesc) == 24, "FrameDesc");
+static_assert(sizeof(UnframeDesc) == 24, "UnframeDesc");
+static_assert(sizeof(UnframeOut) == 8, "UnframeOut");
+static_assert(sizeof(TailDesc) == 16, "TailDesc");
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -45,6 +58,9 @@ __global__ void tamd_host_copy(const HostCopyDesc*, uint32_t, uint8_t*, uint32_t
 __global__ void tamd_copy_in(const uint4*, uint4*, uint32_t, const uint4*, uint4*, uint32_t);
 __global__ void tamd_digest_rows(const DigestDesc*, uint32_t, const uint8_t*, unsigned long long*);
 __global__ void tamd_verify_rows(const VerifyDesc*, uint32_t, const uint8_t*, VerifyOut*);
+__global__ void tamd_frame_rows(const FrameDesc*, uint32_t, uint8_t*, uint32_t);
+__global__ void tamd_unframe_rows(const UnframeDesc*, uint32_t, const uint8_t*, uint64_t, UnframeOut*, uint32_t, uint32_t);
+__global__ void tamd_gather_tails(const TailDesc*, uint32_t, uint8_t*);
 __global__ void tamd_timed_region();
 __global__ void tamd_nop();
 }
