@@ -131,11 +131,13 @@ void Decoder::append(uint32_t e0, const RowId* rows, uint32_t k, uint32_t framed
             return;
         }
     }
+    // (a run with a layout names its first handle only)
+    auto row_at = [&](uint32_t x) { return layout ? rows[0] + x : rows[x]; };
     uint32_t j = 0;
     while (j < k) {
         Segment* last = segs_.empty() ? nullptr : &segs_.back();
         const uint32_t e_abs = e + base_;
-        const RowId r = rows[j];
+        const RowId r = row_at(j);
         const uint32_t off = rt.offset(r);
         const bool cont = last && last->end() == e_abs && last->bytes == framed_bytes &&
                           last->header_bytes == header_bytes && last->owned == owned && r == last->row0 + last->count &&
@@ -164,7 +166,7 @@ void Decoder::append(uint32_t e0, const RowId* rows, uint32_t k, uint32_t framed
         // the rest of the run while rows keep both strides: only the element's segment number
         if (last->count >= 2) {
             uint32_t n = last->count;
-            while (j < k && rows[j] == last->row0 + n && col != 0 && rt.offset(rows[j]) == last->off(n)) {
+            while (j < k && row_at(j) == last->row0 + n && col != 0 && rt.offset(row_at(j)) == last->off(n)) {
                 subs_[e / kSubwindow]->seg[e % kSubwindow] = id;
                 ++e;
                 ++j;
@@ -1383,13 +1385,8 @@ bool Decoder::eliminate_direct(Recovery* rec, uint32_t sum_elem, Sym& buf) {
         dpairs_.resize(keep);
         sort_pair_keys(dpairs_);
     }
-    uint64_t ops = 0;
-    uint8_t lk[kLanes][3];
-    for (unsigned l = 0; l < kLanes; ++l) {
-        const unsigned op = row_opcode(l, m.Row);
-        ops |= (uint64_t)op << (6 * l);
-        opcode_coefs(op, rx, lk[l]);
-    }
+    const uint64_t ops = g_gf.row_ops[m.Row];
+    const uint8_t (*lk)[3] = g_gf.row_lk[m.Row];
     // Batched sessions (Context::dense_split) cut the range into chunks of `split` elements from
     // sum_elem, each one op that stores its partial sum (level 1, a shareable combine) and enters
     // the row as one term: one work item never walks hundreds of packets (a launch's tail), as

@@ -41,7 +41,8 @@ public:
                         bool* took_ownership);
     // Batched in-order add_original of columns col0 .. col0 + k - 1 (equal lengths, rows[0..k))
     // while no recovery packet is pending, when is_ready() cannot succeed after any of them.
-    // Returns false, with nothing done, when that does not hold.
+    // Returns false, with nothing done, when that does not hold.  `layout` as Encoder::add_run's
+    // (only rows[0] is read then).
     bool add_run_inorder(uint32_t col0, const RowId* rows, uint32_t k, uint32_t framed_bytes,
                          uint32_t header_bytes, uint32_t payload_bytes, bool borrowed,
                          uint64_t layout = 0);

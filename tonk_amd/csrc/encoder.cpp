@@ -49,8 +49,66 @@ void Encoder::drop_all() {
     held_ = 0;
     seg_base_ += (uint32_t)segs_.size();
     segs_.clear();
-    win_.clear();
+    times_.clear();
+    wsize_ = 0;
     base_ = 0;
+}
+
+size_t Encoder::time_index(uint32_t e) const {
+    const uint32_t a = base_ + e;
+    const size_t n = times_.size();
+    auto holds = [&](size_t i) {
+        return (int32_t)(a - times_[i].first) >= 0 && (i + 1 == n || (int32_t)(a - times_[i + 1].first) < 0);
+    };
+    size_t i = time_cur_;
+    if (i < n && holds(i)) return i;
+    if (++i < n && holds(i)) return time_cur_ = i;
+    size_t lo = 0, hi = n;  // the last run that starts at or before a
+    while (hi - lo > 1) {
+        const size_t mid = (lo + hi) / 2;
+        if ((int32_t)(a - times_[mid].first) >= 0) lo = mid;
+        else hi = mid;
+    }
+    return time_cur_ = lo;
+}
+
+void Encoder::push_time(uint32_t abs_first, uint32_t msec) {
+    if (times_.empty() || times_.back().msec != msec) times_.push_back(TimeRun{abs_first, msec});
+}
+
+// The run holding e becomes up to three: the elements before e, e alone, those after it.  Equal
+// neighbours merge again, so elements resent at one time stay one run.
+void Encoder::set_msec(uint32_t e, uint32_t msec) {
+    size_t i = time_index(e);
+    if (times_[i].msec == msec) return;
+    const uint32_t a = base_ + e;
+    const uint32_t old = times_[i].msec;
+    const uint32_t end = i + 1 < times_.size() ? times_[i + 1].first : base_ + wsize_;
+    if ((int32_t)(a - times_[i].first) > 0) {  // (a first run that begins below the window included)
+        times_.insert(times_.begin() + (i + 1), TimeRun{a, msec});
+        ++i;
+    } else if (i > 0 && times_[i - 1].msec == msec) {
+        times_.erase(times_.begin() + i);  // e joins the run before it
+        --i;
+    } else {
+        times_[i] = TimeRun{a, msec};
+    }
+    // run i now ends with e; what followed e in the old run keeps the old time
+    if (a + 1 != end) {
+        times_.insert(times_.begin() + (i + 1), TimeRun{a + 1, old});
+    } else if (i + 1 < times_.size() && times_[i + 1].msec == msec) {
+        times_.erase(times_.begin() + (i + 1));
+    }
+}
+
+uint32_t Encoder::longest_age(uint32_t lo, uint32_t hi, uint32_t now, uint32_t longest) const {
+    if (lo >= hi) return longest;
+    const uint32_t end = base_ + hi;
+    for (size_t i = time_index(lo); i < times_.size() && (int32_t)(times_[i].first - end) < 0; ++i) {
+        const int32_t d = (int32_t)(now - times_[i].msec);
+        if ((uint32_t)d > longest && d > 0) longest = (uint32_t)d;
+    }
+    return longest;
 }
 
 StoredOriginal Encoder::view(uint32_t e) const {
@@ -60,7 +118,7 @@ StoredOriginal Encoder::view(uint32_t e) const {
     o.row = s.row(j);
     o.bytes = s.bytes;
     o.column = to_column(e);
-    o.send_msec = win_[e].send_msec;
+    o.send_msec = msec_of(e);
     o.off = s.off(j);
     o.header_bytes = s.header_bytes;
     o.owned = s.owned;
@@ -77,15 +135,12 @@ void Encoder::pre_flush() {
 void Encoder::append(const RowId* rows, uint32_t k, uint32_t framed_bytes, uint32_t header_bytes, uint8_t owned,
                      void* host, uint32_t now, uint64_t layout) {
     const RowTable& rt = ctx_->rows;
-    uint32_t e_abs = base_ + (uint32_t)win_.size();
+    uint32_t e_abs = base_ + wsize_;
     uint32_t col = next_column_;
-    win_.reserve_more(k);
-    Slot* wb = win_.slot_base();
-    const size_t mask = win_.slot_mask();
-    size_t idx = win_.slot_index(win_.size());
+    push_time(e_abs, now);
+    wsize_ += k;
     // Fast path: the k packets are consecutive handles at one offset stride with no column wrap
-    // inside (a stretch of a session's inputs): they continue the last segment or open one, and
-    // only the element slots are filled.
+    // inside (a stretch of a session's inputs): they continue the last segment or open one.
     if (k >= 2 && !host && col + k - 1 < kColumnPeriod && col != 0 && (layout || consecutive_handles(rows, k))) {
         const uint32_t o0 = layout ? (uint32_t)(layout >> 32) : rt.offset(rows[0]);
         const uint32_t o1 = layout ? o0 + (uint32_t)layout : rt.offset(rows[1]);
@@ -114,17 +169,16 @@ void Encoder::append(const RowId* rows, uint32_t k, uint32_t framed_bytes, uint3
                 segs_.push_back(sg);
                 if (owned) ++held_;
             }
-            const Slot v{seg_base_ + (uint32_t)segs_.size() - 1, now};
-            for (uint32_t x = 0; x < k; ++x) wb[(idx + x) & mask] = v;
-            win_.commit(k);
             return;
         }
     }
+    // (a run with a layout names its first handle only)
+    auto row_at = [&](uint32_t x) { return layout ? rows[0] + x : rows[x]; };
     uint32_t j = 0;
     while (j < k) {
         // extend the last segment when this packet continues it, else open one
         Segment* last = segs_.empty() ? nullptr : &segs_.back();
-        const RowId r = rows[j];
+        const RowId r = row_at(j);
         const uint32_t off = rt.offset(r);
         const bool cont = last && !host && !last->host && last->row0 != kNoRow && last->end() == e_abs &&
                           last->bytes == framed_bytes && last->header_bytes == header_bytes && last->owned == owned &&
@@ -148,19 +202,14 @@ void Encoder::append(const RowId* rows, uint32_t k, uint32_t framed_bytes, uint3
             if (owned || host) ++held_;
             last = &segs_.back();
         }
-        const uint32_t id = seg_base_ + (uint32_t)segs_.size() - 1;
-        wb[idx] = Slot{id, now};
-        idx = (idx + 1) & mask;
         ++e_abs;
         col = col_inc(col);
         ++j;
         // the rest of the run while rows keep both strides (one contiguous scan of the handles'
-        // offsets): only the per-element slot is written
+        // offsets)
         if (last->count >= 2) {
             uint32_t n = last->count;
-            while (j < k && rows[j] == last->row0 + n && col != 0 && rt.offset(rows[j]) == last->off(n)) {
-                wb[idx] = Slot{id, now};
-                idx = (idx + 1) & mask;
+            while (j < k && row_at(j) == last->row0 + n && col != 0 && rt.offset(row_at(j)) == last->off(n)) {
                 ++n;
                 ++j;
                 col = col_inc(col);
@@ -169,7 +218,6 @@ void Encoder::append(const RowId* rows, uint32_t k, uint32_t framed_bytes, uint3
             last->count = n;
         }
     }
-    win_.commit(k);
 }
 
 // EncoderPacketWindow::Add (SiameseEncoder.cpp:85-161)
@@ -199,8 +247,8 @@ uint32_t Encoder::add_first(RowId row, uint32_t framed_bytes, uint32_t header_by
             ph.count = element;
             ph.column0 = column - element;
             segs_.push_back(ph);
-            for (uint32_t e = 0; e < element; ++e)
-                win_.push_back(Slot{seg_base_ + (uint32_t)segs_.size() - 1, placeholder_msec_[e]});
+            for (uint32_t e = 0; e < element; ++e) push_time(base_ + e, placeholder_msec_[e]);
+            wsize_ = element;
         }
     }
     append(&row, 1, framed_bytes, header_bytes, borrowed ? 0 : 1, host, now);
@@ -233,12 +281,16 @@ bool Encoder::add_run(const RowId* rows, uint32_t k, uint32_t framed_bytes, uint
     count_ += m;
     const uint32_t first = next_column_;
     next_column_ = col_add(next_column_, m);
-    // every lane one of these columns fell on (all m have the same length)
-    for (uint32_t j = 0; j < m && j < kLanes; ++j) {
-        Lane& lane = lanes_[(first + j) % kLanes];
-        if (lane.longest < framed_bytes) lane.longest = framed_bytes;
+    // every lane one of these columns fell on (all m have the same length), unless none of the
+    // lanes is below it
+    if (framed_bytes > lanes_longest_min_) {
+        for (uint32_t j = 0; j < m && j < kLanes; ++j) {
+            Lane& lane = lanes_[(first + j) % kLanes];
+            if (lane.longest < framed_bytes) lane.longest = framed_bytes;
+        }
+        if (m >= kLanes) lanes_longest_min_ = framed_bytes;  // (each lane got one)
+        if (longest_ < framed_bytes) longest_ = framed_bytes;
     }
-    if (longest_ < framed_bytes) longest_ = framed_bytes;
     stats_[0] += m;
     stats_[1] += (uint64_t)payload_bytes * m;
     return true;
@@ -248,7 +300,7 @@ bool Encoder::add_run(const RowId* rows, uint32_t k, uint32_t framed_bytes, uint
 void Encoder::start_new_window(uint32_t column) {
     // Everything from the previous window is unreachable once Count reached zero (only the send
     // timestamps of its first elements stay visible to the RTT scan, see placeholder_msec_).
-    for (uint32_t e = 0; e < kLanes; ++e) placeholder_msec_[e] = e < win_.size() ? win_[e].send_msec : placeholder_msec_[e];
+    for (uint32_t e = 0; e < kLanes && e < wsize_; ++e) placeholder_msec_[e] = msec_of(e);
     ++window_gen_;  // (a pending Cauchy group does not extend into the new window)
     drop_all();
     const uint32_t element = column % kLanes;
@@ -259,6 +311,7 @@ void Encoder::start_new_window(uint32_t column) {
     count_ = element + 1;
     longest_ = 0;
     for (unsigned l = 0; l < kLanes; ++l) lanes_[l].longest = 0;
+    lanes_longest_min_ = 0;
 }
 
 // EncoderPacketWindow::RemoveBefore (SiameseEncoder.cpp:183-216)
@@ -330,8 +383,11 @@ void Encoder::remove_elements() {
     // segments below `drop` leave (what they own is released); one that straddles it keeps its
     // later packets
     drop_segments_below(drop);
-    win_.pop_front(removed);
+    wsize_ -= removed;
     base_ = cut;
+    size_t gone = 0;  // time runs that end at or below the window start
+    while (gone + 1 < times_.size() && (int32_t)(times_[gone + 1].first - base_) <= 0) ++gone;
+    if (gone) times_.erase(times_.begin(), times_.begin() + gone);
     count_ -= removed;
     column_start_ = to_column(removed);
     first_unremoved_ -= removed;
@@ -340,7 +396,7 @@ void Encoder::remove_elements() {
     uint32_t longest = 0, lane_longest[kLanes] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (first_unremoved_ < count_) {
         const uint32_t lo = base_ + first_unremoved_, hi = base_ + count_;
-        for (uint32_t i = win_[first_unremoved_].seg - seg_base_; i < segs_.size(); ++i) {
+        for (size_t i = seg_index_at(lo); i < segs_.size(); ++i) {
             const Segment& sg = segs_[i];
             if (sg.first >= hi) break;
             const uint32_t a = sg.first > lo ? sg.first : lo, b = sg.end() < hi ? sg.end() : hi;
@@ -353,7 +409,11 @@ void Encoder::remove_elements() {
         }
     }
     longest_ = longest;
-    for (unsigned l = 0; l < kLanes; ++l) lanes_[l].longest = lane_longest[l];
+    lanes_longest_min_ = ~0u;
+    for (unsigned l = 0; l < kLanes; ++l) {
+        lanes_[l].longest = lane_longest[l];
+        if (lanes_longest_min_ > lane_longest[l]) lanes_longest_min_ = lane_longest[l];
+    }
 
     if (sum_end_ <= sum_start_) reset_sums(first_unremoved_);
 }
@@ -457,9 +517,10 @@ void Encoder::update_rto() {
     uint32_t element = to_element(ack_.next_rto_column);
     if (element >= window_count) element = first_unremoved_;
 
-    for (; element < first_loss; ++element) {
-        const int32_t d = (int32_t)(now - win_[element].send_msec);
-        if ((uint32_t)d > longest && d > 0) longest = (uint32_t)d;
+    // (the oldest send time of a range: one look per time run it overlaps)
+    if (element < first_loss) {
+        longest = longest_age(element, first_loss, now, longest);
+        element = first_loss;
     }
 
     uint32_t remaining = ack_.data_bytes;
@@ -472,10 +533,10 @@ void Encoder::update_rto() {
         remaining -= (uint32_t)n;
         if (element + 1 < first_loss) element = first_loss - 1;
         first_loss += rel;
-        for (; element < first_loss; ++element) {
-            if (element >= window_count) return;
-            const int32_t d = (int32_t)(now - win_[element].send_msec);
-            if ((uint32_t)d > longest && d > 0) longest = (uint32_t)d;
+        if (element < first_loss) {
+            if (first_loss > window_count) return;  // (the range leaves the window)
+            longest = longest_age(element, first_loss, now, longest);
+            element = first_loss;
         }
         first_loss += lossM1 + 2;
     }
@@ -559,9 +620,8 @@ Result Encoder::retransmit(StoredOriginal* out) {
     if (ack_.found_oldest) {
         const uint32_t e = col_sub(ack_.oldest_column, column_start_);
         if (!col_delta_negative(e) && e >= first && e < count) {
-            Slot& o = win_[e];
-            if ((uint32_t)(now - o.send_msec) < rto) return kNeedMoreData;
-            o.send_msec = now;
+            if ((uint32_t)(now - msec_of(e)) < rto) return kNeedMoreData;
+            set_msec(e, now);
             ack_.found_oldest = false;
             return attempt_retransmit(e, out);
         }
@@ -570,9 +630,9 @@ Result Encoder::retransmit(StoredOriginal* out) {
 
     uint32_t nack_element = first;
     uint32_t oldest = nack_element;
-    uint32_t oldest_msec = win_[oldest].send_msec;
+    uint32_t oldest_msec = msec_of(oldest);
     if ((uint32_t)(now - oldest_msec) >= rto) {
-        win_[oldest].send_msec = now;
+        set_msec(oldest, now);
         return attempt_retransmit(oldest, out);
     }
 
@@ -582,10 +642,9 @@ Result Encoder::retransmit(StoredOriginal* out) {
         while (next_loss_column(column)) {
             nack_element = to_element(column);
             if (nack_element >= count) break;
-            Slot& o = win_[nack_element];
-            const uint32_t last = o.send_msec;
+            const uint32_t last = msec_of(nack_element);
             if ((uint32_t)(now - last) >= rto) {
-                o.send_msec = now;
+                set_msec(nack_element, now);
                 return attempt_retransmit(nack_element, out);
             }
             if ((int32_t)(oldest_msec - last) > 0) { oldest = nack_element; oldest_msec = last; }
@@ -593,10 +652,9 @@ Result Encoder::retransmit(StoredOriginal* out) {
     }
 
     for (uint32_t e = nack_element + 1; e < count; ++e) {
-        Slot& o = win_[e];
-        const uint32_t last = o.send_msec;
+        const uint32_t last = msec_of(e);
         if ((uint32_t)(now - last) >= rto) {
-            o.send_msec = now;
+            set_msec(e, now);
             return attempt_retransmit(e, out);
         }
         if ((int32_t)(oldest_msec - last) > 0) { oldest = e; oldest_msec = last; }
@@ -678,7 +736,7 @@ Result Encoder::generate_cauchy(RecoveryOut& out) {
     uint32_t used = 0;
     {
         const uint32_t lo = base_ + first, hi = base_ + count_;
-        for (uint32_t i = win_[first].seg - seg_base_; i < segs_.size(); ++i) {
+        for (size_t i = seg_index_at(lo); i < segs_.size(); ++i) {
             const Segment& sg = segs_[i];
             if (sg.first >= hi) break;
             const uint32_t a = sg.first > lo ? sg.first : lo, b = sg.end() < hi ? sg.end() : hi;
@@ -833,8 +891,7 @@ bool Encoder::defer_dense(uint32_t row, uint32_t recovery_bytes, const RecoveryO
     }
     DenseTarget& t = dgrp_[dgrp_n_];
     t.row = out.row;
-    t.ops = 0;
-    for (unsigned l = 0; l < kLanes; ++l) t.ops |= (uint64_t)row_opcode(l, row) << (6 * l);
+    t.ops = g_gf.row_ops[row];
     t.rx = row_value(row);
     t.hi = hi - lo;
     t.flen = out.footer_len;

@@ -103,7 +103,7 @@ public:
     // add() calls.  Returns false, with nothing done, when one of those calls would not succeed.
     // `layout` (nonzero): the caller guarantees rows[j] == rows[0] + j at arena offsets
     // layout >> 32 + j * (layout & 0xffffffff) (a stretch of a session's input rows), so neither
-    // is checked nor looked up.
+    // is checked nor looked up, and only rows[0] and rows[1] are read.
     bool add_run(const RowId* rows, uint32_t k, uint32_t framed_bytes, uint32_t header_bytes,
                  uint32_t payload_bytes, bool borrowed, uint32_t* first_col,
                  uint64_t layout = 0);
@@ -163,27 +163,57 @@ private:
     uint64_t now_msec() const;
 
     // ---- EncoderPacketWindow (SiameseEncoder.h:104-232) ----
-    // Elements are stored as segments (Segment, above); per element only its segment number and
-    // its send time (retransmit moves single elements' send times).
-    struct Slot { uint32_t seg, send_msec; };
-    Ring<Slot> win_;
+    // Elements are stored as segments (Segment, above), which tile the elements from the first
+    // kept one to the window end, and their send times as time runs: nothing is kept per element,
+    // so adding k packets costs the same for every k.
     Ring<Segment> segs_;       // in element order; segs_[i] is segment number seg_base_ + i
     uint32_t seg_base_ = 0;    // number of the segment at segs_[0]
     uint32_t base_ = 0;        // absolute element number of window element 0
-    const Segment& seg_of(uint32_t e) const { return segs_[win_[e].seg - seg_base_]; }
+    uint32_t wsize_ = 0;       // elements stored (count_, until remove_before empties the window)
+    // Send times: run i is the absolute elements [times_[i].first, times_[i + 1].first), the last
+    // one up to the window end, all sent at `msec` (an add at the last run's time extends it by
+    // appending nothing; retransmit moves single elements' times and splits a run).  The first
+    // run may begin below the window.
+    struct TimeRun { uint32_t first, msec; };
+    std::vector<TimeRun> times_;
+    mutable size_t time_cur_ = 0;  // the run the last lookup found (walks are sequential)
+    mutable size_t seg_cur_ = 0;   // likewise, the segment (as an index in segs_)
+    size_t time_index(uint32_t e) const;        // the run holding window element e
+    uint32_t msec_of(uint32_t e) const { return times_[time_index(e)].msec; }
+    void set_msec(uint32_t e, uint32_t msec);   // one element's send time
+    void push_time(uint32_t abs_first, uint32_t msec);  // elements from abs_first on (appended next)
+    // max(longest, now - send time) over window elements [lo, hi), positive differences only
+    uint32_t longest_age(uint32_t lo, uint32_t hi, uint32_t now, uint32_t longest) const;
+    // Index in segs_ of the segment holding absolute element `a`, inside the window or below it
+    // (segments below the window are kept while the running sums may still need them, see
+    // remove_elements): the last lookup's segment or its successor, else a binary search (a
+    // session's window holds about ten).  Every segment holds a packet or more, so the one a's
+    // distance from the first segment names bounds the search, and is the answer itself in a window
+    // of single packets (the C ABI's thousands of one-packet segments: the LDPC pairs' random
+    // reads stay one look each).
+    size_t seg_index_at(uint32_t a) const {
+        const size_t n = segs_.size();
+        size_t i = seg_cur_;
+        if (i < n && a - segs_[i].first < segs_[i].count) return i;
+        if (++i < n && a - segs_[i].first < segs_[i].count) return seg_cur_ = i;
+        size_t lo = 0, hi = n;  // the last segment that starts at or before a
+        if (n && (int32_t)(a - segs_[0].first) >= 0 && a - segs_[0].first < n) {
+            hi = a - segs_[0].first + 1;
+            if ((int32_t)(a - segs_[hi - 1].first) >= 0) return seg_cur_ = hi - 1;
+        }
+        while (hi - lo > 1) {
+            const size_t mid = (lo + hi) / 2;
+            if ((int32_t)(a - segs_[mid].first) >= 0) lo = mid;
+            else hi = mid;
+        }
+        return seg_cur_ = lo;
+    }
+    const Segment& seg_of(uint32_t e) const { return segs_[seg_index_at(base_ + e)]; }
     RowId row_of(uint32_t e) const {
         const Segment& s = seg_of(e);
         return s.row(e + base_ - s.first);
     }
     StoredOriginal view(uint32_t e) const;  // element e as a value (get / retransmit)
-    // Index in segs_ of the segment holding absolute element `a` (segments below the window are
-    // kept while the running sums may still need them, see remove_elements).
-    size_t seg_index_at(uint32_t a) const {
-        if ((int32_t)(a - base_) >= 0) return win_[a - base_].seg - seg_base_;
-        size_t i = 0;
-        while (i + 1 < segs_.size() && (int32_t)(segs_[i].end() - a) <= 0) ++i;
-        return i;
-    }
     uint32_t sum_abs_start() const { return base_ + sum_start_ - sum_erased_; }  // first element of the sums
     // Append k packets (rows[0..k), equally long) at the window end, extending the last segment
     // while the rows continue its strides; `now` is their send time.
@@ -201,6 +231,9 @@ private:
     uint32_t placeholder_msec_[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     uint32_t next_column_ = 0, count_ = 0, column_start_ = 0, longest_ = 0;
     uint32_t held_ = 0;  // segments with something to release (owned rows or a host copy)
+    // A lower bound of every lane's `longest`: an add of packets no longer than this raises none
+    // of them (equal lengths: every add after the window's first eight packets).
+    uint32_t lanes_longest_min_ = 0;
     uint32_t first_unremoved_ = 0;
     uint32_t sum_start_ = 0, sum_end_ = 0, sum_column_start_ = 0, sum_erased_ = 0;
     // The reference advances each of a lane's three sums lazily on its own; their values only
@@ -233,7 +266,7 @@ public:
     int debug_state(char* buf, size_t n) const {
         const uint32_t now = (uint32_t)now_msec();
         const uint32_t first = col_sub(ack_.next_expected, column_start_);
-        const uint32_t age = first < count_ && first < win_.size() ? now - win_[first].send_msec : 0;
+        const uint32_t age = first < count_ && first < wsize_ ? now - msec_of(first) : 0;
         return snprintf(buf, n,
                         "count=%u first_unremoved=%u next_column=%u column_start=%u ack_next=%u ack_bytes=%u "
                         "rto=%u found_oldest=%d first_age_ms=%u disabled=%d",

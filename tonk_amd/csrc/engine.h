@@ -527,10 +527,6 @@ private:
 inline uint8_t sum_coef(unsigned s, uint8_t cx) { return s == 0 ? 1 : (s == 1 ? cx : gf_sqr(cx)); }
 // Coefficients of the lane sums a Siamese row reads (SiameseEncoder.cpp:1046-1098): opcode bit s
 // adds sum s to the row, bit s + 3 adds it to the product that is multiplied by RX.
-inline void opcode_coefs(unsigned op, uint8_t rx, uint8_t* c) {
-    for (unsigned s = 0; s < 3; ++s)
-        c[s] = (uint8_t)(((op >> s) & 1u) ^ (((op >> (s + 3)) & 1u) ? rx : 0u));
-}
 
 // Symbolic content of rows written by the pending program, so readers in the same flush can
 // use the content's terms instead of the row itself (which would add a level).

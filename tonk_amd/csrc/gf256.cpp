@@ -69,6 +69,14 @@ bool gf_init() {
         g_gf.perm[c][6] = 0;
         g_gf.perm[c][7] = 0;
     }
+    for (unsigned row = 0; row < 256; ++row) {
+        g_gf.row_ops[row] = 0;
+        for (unsigned l = 0; l < kLanes; ++l) {
+            const unsigned op = row_opcode(l, row);
+            g_gf.row_ops[row] |= (uint64_t)op << (6 * l);
+            opcode_coefs(op, row_value(row), g_gf.row_lk[row][l]);
+        }
+    }
     g_gf.ready = self_test();
     return g_gf.ready;
 }

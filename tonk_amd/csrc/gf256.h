@@ -19,6 +19,11 @@ struct GF {
     // Per-coefficient product tables for the device: x * c = T0[x & 7] ^ T1[(x >> 3) & 7] ^
     // T2[x >> 6], each table 8 bytes (T2 uses 4).  Laid out as 6 dwords per coefficient.
     uint32_t perm[256][8];
+    // Per recovery row (a Siamese row number is below kRowPeriod; a received one is a byte): the
+    // eight lanes' opcodes, 6 bits each, and their sum coefficients (row_opcode, opcode_coefs
+    // with the row's RX value).
+    uint64_t row_ops[256];
+    uint8_t row_lk[256][8][3];
     bool ready = false;
 };
 
@@ -60,6 +65,13 @@ inline unsigned row_opcode(unsigned lane, unsigned row) {
     k ^= (k >> 16);
     const uint32_t op = k & 63u;
     return op == 0 ? 16u : op;
+}
+
+// The coefficients of a lane's three sums in a row with opcode `op` and RX value `rx`: bit s
+// takes sum s, bit s + 3 takes RX times sum s.
+inline void opcode_coefs(unsigned op, uint8_t rx, uint8_t* c) {
+    for (unsigned s = 0; s < 3; ++s)
+        c[s] = (uint8_t)(((op >> s) & 1u) ^ (((op >> (s + 3)) & 1u) ? rx : 0u));
 }
 
 inline uint8_t cauchy_element(unsigned row, unsigned column) {

@@ -22,10 +22,19 @@ struct ResidentBackend {
     Context* ctx = nullptr;
     std::unique_ptr<Encoder> enc;
     std::unique_ptr<Decoder> dec;
-    std::vector<RowId> enc_rows, dec_rows;
     uint32_t pool = 0;        // input rows per side (original i reads row i mod pool)
     bool pool_affine = false; // each side's pool rows are consecutive handles at one arena stride:
     uint32_t pool_off[2] = {0, 0}, pool_stride = 0;  // row i mod pool at pool_off[side] + (i mod pool) * stride
+    RowId pool_row0[2] = {kNoRow, kNoRow};           // and its handle is pool_row0[side] + (i mod pool)
+    // Only when the pool is not affine (an arena that could not place the rows back to back): the
+    // handle of every original, per side.  An affine pool computes them.
+    std::vector<RowId> rows_[2];
+    uint32_t pool_mask = 0;   // pool - 1 when the pool is a power of two: i mod pool is one AND
+    // Otherwise the adds' running position: they are sequential, so the next call's index is where
+    // the last one ended, and its i mod pool is kept instead of divided out.
+    struct Cursor { uint32_t index = ~0u, slot = 0; } cur_[2];
+    RowId run_rows_[2];              // the first two handles of a run whose layout is given
+    std::vector<RowId> run_scratch_; // all of them, for a run the codecs check themselves
     bool nobatch = false;     // tools' nobatch=1: single adds only (the runner's fallback path)
     bool contig = true;       // tools' contig=0: the codecs check every run's contiguity themselves
     uint64_t alg_bytes = 0, payload_bytes = 0;
@@ -36,37 +45,76 @@ struct ResidentBackend {
     // one ACCR instruction per run); original i >= pool_n reads the row of i - pool_n.  False
     // when the arena is full.
     bool alloc_inputs(uint32_t n, uint32_t pool_n, uint32_t row_bytes) {
-        enc_rows.assign(n, kNoRow);
-        dec_rows.assign(n, kNoRow);
         for (int side = 0; side < 2; ++side) {
-            std::vector<RowId>& rows = side ? dec_rows : enc_rows;
+            std::vector<RowId>& rows = rows_[side];
+            rows.assign(pool_n, kNoRow);
             for (uint32_t i = 0; i < pool_n; ++i)
                 if ((rows[i] = ctx->alloc(row_bytes)) == kNoRow) return false;
-            for (uint32_t i = pool_n; i < n; ++i) rows[i] = rows[i - pool_n];
         }
         pool = pool_n;
+        pool_mask = pool && !(pool & (pool - 1)) ? pool - 1 : 0;
         pool_affine = pool >= 2;
         for (int side = 0; side < 2 && pool_affine; ++side) {
-            const std::vector<RowId>& rows = side ? dec_rows : enc_rows;
+            const std::vector<RowId>& rows = rows_[side];
             const uint32_t o0 = ctx->rows.offset(rows[0]), stride = ctx->rows.offset(rows[1]) - o0;
             pool_affine = consecutive_handles(rows.data(), pool) && stride > 0 &&
                           ctx->rows.affine(rows[0], pool, stride) && (!side || stride == pool_stride);
             pool_off[side] = o0;
+            pool_row0[side] = rows[0];
             pool_stride = stride;
+        }
+        for (int side = 0; side < 2; ++side) {
+            std::vector<RowId>& rows = rows_[side];
+            if (pool_affine) {
+                std::vector<RowId>().swap(rows);  // (computed: row())
+            } else {
+                rows.resize(n);
+                for (uint32_t i = pool_n; i < n; ++i) rows[i] = rows[i - pool_n];
+            }
         }
         return true;
     }
-    // A run that does not wrap the input pool is consecutive handles at one stride: the codecs
-    // get its layout instead of checking and looking it up (the row table is cold).
-    uint64_t layout(int side, uint32_t index, uint32_t k) const {
-        if (!pool_affine || !contig || index % pool + k > pool) return 0;
-        return (uint64_t)(pool_off[side] + (index % pool) * pool_stride) << 32 | pool_stride;
+    // The input row of original `index` on a side (0: encoder, 1: decoder).
+    RowId row(int side, uint32_t index) const {
+        if (!pool_affine) return rows_[side][index];
+        return pool_row0[side] + (pool_mask ? index & pool_mask : index % pool);
+    }
+    // index mod pool for an add of k originals from `index` on.
+    uint32_t pool_slot(int side, uint32_t index, uint32_t k) {
+        if (pool_mask) return index & pool_mask;
+        Cursor& c = cur_[side];
+        const uint32_t slot = c.index == index ? c.slot : index % pool;
+        c.index = index + k;
+        c.slot = slot + k;
+        if (c.slot >= pool) c.slot = c.slot - pool < pool ? c.slot - pool : c.slot % pool;
+        return slot;
+    }
+    // The handles of a run (rows[0..k)) and its layout.  A run that does not wrap the input pool
+    // is consecutive handles at one stride: the codecs get its layout instead of checking and
+    // looking it up (the row table is cold), and read rows[0] (rows[1] for what follows a window's
+    // first packet) only.  Any other run gets every handle and layout 0.
+    const RowId* run_rows(int side, uint32_t index, uint32_t k, uint64_t* layout) {
+        *layout = 0;
+        if (!pool_affine) return &rows_[side][index];
+        const uint32_t slot = pool_slot(side, index, k);
+        if (contig && slot + k <= pool) {
+            *layout = (uint64_t)(pool_off[side] + slot * pool_stride) << 32 | pool_stride;
+            run_rows_[0] = pool_row0[side] + slot;
+            run_rows_[1] = run_rows_[0] + 1;
+            return run_rows_;
+        }
+        run_scratch_.resize(k);
+        for (uint32_t j = 0, m = slot; j < k; ++j) {
+            run_scratch_[j] = pool_row0[side] + m;
+            if (++m == pool) m = 0;
+        }
+        return run_scratch_.data();
     }
 
     int enc_add(uint32_t index, uint32_t len, uint32_t* col) {
         const uint32_t hb = length_header_bytes(len);
         TAMD_PROF_SCOPE(kEncAdd);
-        const Result r = enc->add(enc_rows[index], hb + len, hb, len, nullptr, col, true);
+        const Result r = enc->add(row(0, index), hb + len, hb, len, nullptr, col, true);
         if (r == kSuccess) {
             alg_bytes += hb + len;
             payload_bytes += len;
@@ -77,7 +125,9 @@ struct ResidentBackend {
         if (nobatch) return false;
         const uint32_t hb = length_header_bytes(len);
         TAMD_PROF_SCOPE(kEncAdd);
-        if (!enc->add_run(&enc_rows[index], k, hb + len, hb, len, true, col0, layout(0, index, k))) return false;
+        uint64_t layout;
+        const RowId* rows = run_rows(0, index, k, &layout);
+        if (!enc->add_run(rows, k, hb + len, hb, len, true, col0, layout)) return false;
         alg_bytes += (uint64_t)(hb + len) * k;
         payload_bytes += (uint64_t)len * k;
         return true;
@@ -86,7 +136,9 @@ struct ResidentBackend {
         if (nobatch) return false;
         const uint32_t hb = length_header_bytes(len);
         TAMD_PROF_SCOPE(kDecAddOrig);
-        if (!dec->add_run_inorder(col0, &dec_rows[index], k, hb + len, hb, len, true, layout(1, index, k))) return false;
+        uint64_t layout;
+        const RowId* rows = run_rows(1, index, k, &layout);
+        if (!dec->add_run_inorder(col0, rows, k, hb + len, hb, len, true, layout)) return false;
         alg_bytes += (uint64_t)(hb + len) * k;
         return true;
     }
@@ -105,7 +157,7 @@ struct ResidentBackend {
         const uint32_t hb = length_header_bytes(len);
         TAMD_PROF_SCOPE(kDecAddOrig);
         bool took = false;
-        const Result r = dec->add_original(col, dec_rows[index], hb + len, hb, len, nullptr, &took, true);
+        const Result r = dec->add_original(col, row(1, index), hb + len, hb, len, nullptr, &took, true);
         alg_bytes += hb + len;
         return r;
     }

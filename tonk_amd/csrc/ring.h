@@ -20,23 +20,9 @@ public:
         buf_[(head_ + n_) & mask_] = v;
         ++n_;
     }
-    // Bulk append: make room for k more, fill slot(n + j) for j < k, then commit(k).
-    void reserve_more(size_t k) {
-        while (n_ + k > buf_.size()) grow();
-    }
-    T* slot_base() { return buf_.data(); }
-    size_t slot_index(size_t i) const { return (head_ + i) & mask_; }
-    size_t slot_mask() const { return mask_; }
-    void commit(size_t k) { n_ += k; }
-    // Append a slot to fill in place (no temporary: a struct built in narrow fields and then
-    // copied with wide loads stalls on store forwarding).
-    T& push_slot() {
-        if (n_ == buf_.size()) grow();
-        return buf_[(head_ + n_++) & mask_];
-    }
     void pop_front(size_t k) {
         if (k > n_) k = n_;
-        // (popped slots keep stale contents: push_back and push_slot rewrite every field)
+        // (popped slots keep stale contents: push_back rewrites every field)
         head_ = (head_ + k) & mask_;
         n_ -= k;
     }

@@ -891,7 +891,7 @@ struct Session {
             if (!n) continue;
             for (int side = 0; side < 2; ++side) {
                 if (!((prm.stage_host >> side) & 1u)) continue;  // (that end's packets are resident)
-                const RowId r = (side ? st.dec_rows : st.enc_rows)[next];
+                const RowId r = st.row(side, next);
                 const uint8_t* src = host_in + (2 * i + side) * side_bytes + (size_t)next * row_cap;
                 dev.h2d((uint64_t)st.ctx->rows.offset(r) * TAMD_ROW_UNIT, src, (size_t)n * row_cap);
                 h2d_bytes += (uint64_t)n * row_cap;
@@ -1117,7 +1117,7 @@ int tamd_session_generate(void* sp) {
         d.reserve(2 * (size_t)pool);
         for (int side = 0; side < 2; ++side)
             for (uint32_t i = 0; i < pool; ++i) {
-                const RowId r = (side ? st.dec_rows : st.enc_rows)[i];
+                const RowId r = st.row(side, i);
                 Device::GenDesc g;
                 g.row = st.ctx->rows.offset(r);
                 g.index = i;
@@ -1152,10 +1152,9 @@ int tamd_session_generate(void* sp) {
             Stream& st = *s->streams[i];
             st.stage = s->prm.stage_host & 3u;
             for (int side = 0; side < 2; ++side) {
-                const std::vector<RowId>& rows = side ? st.dec_rows : st.enc_rows;
-                const uint64_t base = st.ctx->rows.offset(rows[0]);
+                const uint64_t base = st.ctx->rows.offset(st.row(side, 0));
                 for (uint32_t k = 0; k < st.p.n_originals; ++k)
-                    if (st.ctx->rows.offset(rows[k]) != base + (uint64_t)k * (s->row_cap / TAMD_ROW_UNIT)) {
+                    if (st.ctx->rows.offset(st.row(side, k)) != base + (uint64_t)k * (s->row_cap / TAMD_ROW_UNIT)) {
                         s->error = "input rows are not contiguous";
                         return -3;
                     }
