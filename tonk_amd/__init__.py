@@ -273,3 +273,8 @@ class Session:
 from .batch import BatchCodec  # noqa: E402
 
 __all__.append("BatchCodec")
+
+# Seal and open of datagrams in the caller's own device memory (include/tonk_seal.h).
+from .seal import DatagramSealer  # noqa: E402
+
+__all__.append("DatagramSealer")

@@ -18,6 +18,7 @@
 #include "decoder.h"
 #include "device.h"
 #include "frame.h"
+#include "staging.h"
 
 #include <hip/hip_runtime.h>
 
@@ -30,29 +31,6 @@
 using namespace tamd;
 
 namespace {
-
-// A pinned host buffer and its device twin, grown on demand (the device is idle between calls).
-struct Staging {
-    uint8_t* host = nullptr;
-    uint8_t* dev = nullptr;
-    size_t cap = 0;
-    bool ensure(size_t n) {
-        if (n <= cap) return true;
-        release();
-        const size_t want = n + n / 2 + 4096;
-        if (hipHostMalloc((void**)&host, want, hipHostMallocDefault) != hipSuccess) { host = nullptr; return false; }
-        if (hipMalloc((void**)&dev, want) != hipSuccess) { dev = nullptr; release(); return false; }
-        cap = want;
-        return true;
-    }
-    void release() {
-        if (host) hipHostFree(host);
-        if (dev) hipFree(dev);
-        host = dev = nullptr;
-        cap = 0;
-    }
-    ~Staging() { release(); }
-};
 
 enum { kFrame = 0, kUnframe = 1, kTails = 2, kKinds = 3 };
 

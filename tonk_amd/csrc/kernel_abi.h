@@ -1,5 +1,5 @@
 // kernel_abi.h -- the records the helper kernels of kernels.hip read and write, and the
-// prototypes of every kernel the host launches (device.cpp, server.cpp, batch.cpp): one definition for both
+// prototypes of every kernel the host launches (device.cpp, server.cpp, batch.cpp, seal.cpp): one definition for both
 // sides.  The records are plain C; the prototypes need a HIP translation unit.
 #pragma once
 #include <stdint.h>
@@ -29,6 +29,11 @@ typedef struct UnframeDesc { uint64_t dst; uint32_t row, upper, raw, pad; } Unfr
 typedef struct UnframeOut { uint32_t len, status; } UnframeOut;  /* payload bytes, TAMD_FRAME_* (frame.h) */
 /* tamd_gather_tails: the caller's device address of a packet and its bytes; 8 bytes out each */
 typedef struct TailDesc { uint64_t src; uint32_t total, pad; } TailDesc;
+/* tamd_seal_packets (seal.hip): the caller's device address of a datagram, its nonce, stream (the
+   row of the key table), total bytes and ciphered bytes; skip != 0: refused on the host, untouched.
+   One uint32 out each: the result code (seal.h TAMD_SEAL_*), or the plain tag.
+   tamd_gather_footers reads TailDesc records and writes 24 bytes each. */
+typedef struct SealDesc { uint64_t data, nonce; uint32_t stream, bytes, msg, skip; } SealDesc;
 
 static_assert(sizeof(GenDesc) == 24, "GenDesc");
 static_assert(sizeof(GatherDesc) == 12, "GatherDesc");
@@ -41,6 +46,7 @@ static_assert(sizeof(FrameDesc) == 24, "FrameDesc");
 static_assert(sizeof(UnframeDesc) == 24, "UnframeDesc");
 static_assert(sizeof(UnframeOut) == 8, "UnframeOut");
 static_assert(sizeof(TailDesc) == 16, "TailDesc");
+static_assert(sizeof(SealDesc) == 32, "SealDesc");
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -61,6 +67,8 @@ __global__ void tamd_verify_rows(const VerifyDesc*, uint32_t, const uint8_t*, Ve
 __global__ void tamd_frame_rows(const FrameDesc*, uint32_t, uint8_t*, uint32_t);
 __global__ void tamd_unframe_rows(const UnframeDesc*, uint32_t, const uint8_t*, uint64_t, UnframeOut*, uint32_t, uint32_t);
 __global__ void tamd_gather_tails(const TailDesc*, uint32_t, uint8_t*);
+__global__ void tamd_seal_packets(const SealDesc*, uint32_t, const uint32_t*, uint32_t, uint32_t*);
+__global__ void tamd_gather_footers(const TailDesc*, uint32_t, uint8_t*);
 __global__ void tamd_timed_region();
 __global__ void tamd_nop();
 }
