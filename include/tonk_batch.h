@@ -55,6 +55,11 @@ const char* tamd_batch_error(void*);
    with len 0 or above max_packet_bytes gets rc 1 and is skipped. */
 int tamd_batch_encoder_add(void*, uint32_t n, const uint32_t* stream, const uint32_t* len,
                            const void* dev_payloads, uint64_t pitch, uint32_t* packet_num, int32_t* rc);
+/* the same with packet i at dev_payloads + i * pitch + offset[i] (a null offset: all 0, the call
+   above): a span inside a larger slot, such as the reliable messages of a datagram
+   (tonk_datagram.h).  -3 when offset[i] + len[i] > pitch for a packet of valid length. */
+int tamd_batch_encoder_add_at(void*, uint32_t n, const uint32_t* stream, const uint32_t* len, const uint32_t* offset,
+                              const void* dev_payloads, uint64_t pitch, uint32_t* packet_num, int32_t* rc);
 /* one recovery packet per list entry (a stream may appear several times), in list order: packet i
    (data || footer, exactly what siamese_encode returns) at dev_out + i * pitch, bytes[i] long
    (0 unless rc[i] is 0).  pitch >= max_packet_bytes + TAMD_BATCH_RECOVERY_OVERHEAD. */
@@ -66,6 +71,10 @@ int tamd_batch_encoder_ack(void*, uint32_t stream, const uint8_t* data, uint32_t
 /* receiver side */
 int tamd_batch_decoder_add_original(void*, uint32_t n, const uint32_t* stream, const uint32_t* packet_num,
                                     const uint32_t* len, const void* dev_payloads, uint64_t pitch, int32_t* rc);
+/* the same with packet i at dev_payloads + i * pitch + offset[i], as tamd_batch_encoder_add_at */
+int tamd_batch_decoder_add_original_at(void*, uint32_t n, const uint32_t* stream, const uint32_t* packet_num,
+                                       const uint32_t* len, const uint32_t* offset, const void* dev_payloads,
+                                       uint64_t pitch, int32_t* rc);
 /* packet i (data || footer) is bytes[i] long at dev_packets + i * pitch; 0 bytes, or more than
    max_packet_bytes + TAMD_BATCH_RECOVERY_OVERHEAD, gets rc 1 */
 int tamd_batch_decoder_add_recovery(void*, uint32_t n, const uint32_t* stream, const uint32_t* bytes,

@@ -278,3 +278,8 @@ __all__.append("BatchCodec")
 from .seal import DatagramSealer  # noqa: E402
 
 __all__.append("DatagramSealer")
+
+# Message frames and footers of datagrams in the caller's own device memory (include/tonk_datagram.h).
+from .dgram import DatagramFramer  # noqa: E402
+
+__all__.append("DatagramFramer")

@@ -40,6 +40,8 @@ def _lib() -> ctypes.CDLL:
         L.tamd_batch_error.argtypes = [vp]
         for name, args in (
                 ("tamd_batch_encoder_add", [vp, u32, _u32p, _u32p, vp, u64, _u32p, _i32p]),
+                ("tamd_batch_encoder_add_at", [vp, u32, _u32p, _u32p, _u32p, vp, u64, _u32p, _i32p]),
+                ("tamd_batch_decoder_add_original_at", [vp, u32, _u32p, _u32p, _u32p, _u32p, vp, u64, _i32p]),
                 ("tamd_batch_encode", [vp, u32, _u32p, vp, u64, _u32p, _i32p]),
                 ("tamd_batch_encoder_ack", [vp, u32, cp, u32, _u32p]),
                 ("tamd_batch_decoder_add_original", [vp, u32, _u32p, _u32p, _u32p, vp, u64, _i32p]),
@@ -84,15 +86,16 @@ class BatchCodec:
             err = _lib().tamd_batch_error(self._h).decode()
             raise RuntimeError(f"tonk_amd: {what} refused (rc={rc}: {_REFUSED.get(rc, '?')}){': ' + err if err else ''}")
 
-    def encoder_add(self, stream, lens, dev_payloads: int, pitch: int):
-        """Add originals; returns (packet numbers, result codes)."""
+    def encoder_add(self, stream, lens, dev_payloads: int, pitch: int, offset=None):
+        """Add originals (packet i at dev_payloads + i * pitch + offset[i]); returns (packet numbers, result codes)."""
         import numpy as np
         S, L = _u32(stream), _u32(lens)
-        assert S.size == L.size
+        O = None if offset is None else _u32(offset)
+        assert S.size == L.size and (O is None or O.size == S.size)
         pn, rc = np.zeros(S.size, dtype=np.uint32), np.zeros(S.size, dtype=np.int32)
-        self._check(_lib().tamd_batch_encoder_add(self._h, S.size, S.ctypes.data_as(_u32p), L.ctypes.data_as(_u32p),
-                                                  dev_payloads, pitch, pn.ctypes.data_as(_u32p), rc.ctypes.data_as(_i32p)),
-                    "encoder_add")
+        self._check(_lib().tamd_batch_encoder_add_at(self._h, S.size, S.ctypes.data_as(_u32p), L.ctypes.data_as(_u32p),
+                                                     None if O is None else O.ctypes.data_as(_u32p), dev_payloads, pitch,
+                                                     pn.ctypes.data_as(_u32p), rc.ctypes.data_as(_i32p)), "encoder_add")
         return pn, rc
 
     def encode(self, stream, dev_out: int, pitch: int):
@@ -111,15 +114,17 @@ class BatchCodec:
         self._check(rc, "encoder_ack")
         return rc, int(nxt.value)
 
-    def decoder_add_original(self, stream, packet_num, lens, dev_payloads: int, pitch: int):
-        """Add received originals; returns the result codes."""
+    def decoder_add_original(self, stream, packet_num, lens, dev_payloads: int, pitch: int, offset=None):
+        """Add received originals (packet i at dev_payloads + i * pitch + offset[i]); returns the result codes."""
         import numpy as np
         S, P, L = _u32(stream), _u32(packet_num), _u32(lens)
-        assert S.size == P.size == L.size
+        O = None if offset is None else _u32(offset)
+        assert S.size == P.size == L.size and (O is None or O.size == S.size)
         rc = np.zeros(S.size, dtype=np.int32)
-        self._check(_lib().tamd_batch_decoder_add_original(self._h, S.size, S.ctypes.data_as(_u32p), P.ctypes.data_as(_u32p),
-                                                           L.ctypes.data_as(_u32p), dev_payloads, pitch,
-                                                           rc.ctypes.data_as(_i32p)), "decoder_add_original")
+        self._check(_lib().tamd_batch_decoder_add_original_at(self._h, S.size, S.ctypes.data_as(_u32p), P.ctypes.data_as(_u32p),
+                                                              L.ctypes.data_as(_u32p),
+                                                              None if O is None else O.ctypes.data_as(_u32p), dev_payloads,
+                                                              pitch, rc.ctypes.data_as(_i32p)), "decoder_add_original")
         return rc
 
     def decoder_add_recovery(self, stream, nbytes, dev_packets: int, pitch: int):

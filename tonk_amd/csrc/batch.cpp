@@ -279,15 +279,23 @@ const char* tamd_batch_error(void* h) {
 
 int tamd_batch_encoder_add(void* h, uint32_t n, const uint32_t* stream, const uint32_t* len, const void* dev_payloads,
                            uint64_t pitch, uint32_t* packet_num, int32_t* rc) {
+    return tamd_batch_encoder_add_at(h, n, stream, len, nullptr, dev_payloads, pitch, packet_num, rc);
+}
+
+// Packet i at dev_payloads + i * pitch + offset[i] (a null offset: 0).
+int tamd_batch_encoder_add_at(void* h, uint32_t n, const uint32_t* stream, const uint32_t* len, const uint32_t* offset,
+                              const void* dev_payloads, uint64_t pitch, uint32_t* packet_num, int32_t* rc) {
     Batch* b = (Batch*)h;
     if (!b || !stream || !len || !dev_payloads || !packet_num || !rc) return -1;
     std::unique_lock<std::mutex> lk;
     if (const int e = enter(b, lk, n, stream)) return e;
     const uint32_t maxb = b->prm.max_packet_bytes;
     uint32_t largest = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (len[i] <= maxb && len[i] > largest) largest = len[i];
-    if (pitch < largest) return -3;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (len[i] > maxb) continue;
+        if (len[i] > largest) largest = len[i];
+        if (len[i] && (uint64_t)(offset ? offset[i] : 0u) + len[i] > pitch) return -3;
+    }
     if (!b->desc.ensure((size_t)n * sizeof(FrameDesc))) return b->hip(hipErrorOutOfMemory, "staging allocation"), -4;
     FrameDesc* d = (FrameDesc*)b->desc.host;
     size_t nd = 0;
@@ -322,8 +330,8 @@ int tamd_batch_encoder_add(void* h, uint32_t n, const uint32_t* stream, const ui
                 rc[i] = res;
                 packet_num[i] = res == kSuccess ? pn : 0;
                 if (res != kSuccess) { c.rows.free_deferred(r); continue; }
-                d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_payloads + (uint64_t)i * pitch, c.rows.offset(r), l,
-                                    c.rows.cap_bytes(r), 0};
+                d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_payloads + (uint64_t)i * pitch + (offset ? offset[i] : 0u),
+                                    c.rows.offset(r), l, c.rows.cap_bytes(r), 0};
             }
             a += k;
         }
@@ -380,15 +388,23 @@ int tamd_batch_encoder_ack(void* h, uint32_t stream, const uint8_t* data, uint32
 
 int tamd_batch_decoder_add_original(void* h, uint32_t n, const uint32_t* stream, const uint32_t* packet_num,
                                     const uint32_t* len, const void* dev_payloads, uint64_t pitch, int32_t* rc) {
+    return tamd_batch_decoder_add_original_at(h, n, stream, packet_num, len, nullptr, dev_payloads, pitch, rc);
+}
+
+int tamd_batch_decoder_add_original_at(void* h, uint32_t n, const uint32_t* stream, const uint32_t* packet_num,
+                                       const uint32_t* len, const uint32_t* offset, const void* dev_payloads, uint64_t pitch,
+                                       int32_t* rc) {
     Batch* b = (Batch*)h;
     if (!b || !stream || !packet_num || !len || !dev_payloads || !rc) return -1;
     std::unique_lock<std::mutex> lk;
     if (const int e = enter(b, lk, n, stream)) return e;
     const uint32_t maxb = b->prm.max_packet_bytes;
     uint32_t largest = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (len[i] <= maxb && len[i] > largest) largest = len[i];
-    if (pitch < largest) return -3;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (len[i] > maxb) continue;
+        if (len[i] > largest) largest = len[i];
+        if (len[i] && (uint64_t)(offset ? offset[i] : 0u) + len[i] > pitch) return -3;
+    }
     if (!b->desc.ensure((size_t)n * sizeof(FrameDesc))) return b->hip(hipErrorOutOfMemory, "staging allocation"), -4;
     FrameDesc* d = (FrameDesc*)b->desc.host;
     size_t nd = 0;
@@ -421,8 +437,8 @@ int tamd_batch_decoder_add_original(void* h, uint32_t n, const uint32_t* stream,
                 const Result res = run ? kSuccess : x.dec->add_original(pn0 + j, r, framed, hb, l, nullptr, &took, false);
                 rc[i] = res;
                 if (!took) { c.rows.free_deferred(r); continue; }
-                d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_payloads + (uint64_t)i * pitch, c.rows.offset(r), l,
-                                    c.rows.cap_bytes(r), 0};
+                d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_payloads + (uint64_t)i * pitch + (offset ? offset[i] : 0u),
+                                    c.rows.offset(r), l, c.rows.cap_bytes(r), 0};
             }
             a += k;
         }

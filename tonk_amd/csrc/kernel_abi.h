@@ -34,6 +34,16 @@ typedef struct TailDesc { uint64_t src; uint32_t total, pad; } TailDesc;
    One uint32 out each: the result code (seal.h TAMD_SEAL_*), or the plain tag.
    tamd_gather_footers reads TailDesc records and writes 24 bytes each. */
 typedef struct SealDesc { uint64_t data, nonce; uint32_t stream, bytes, msg, skip; } SealDesc;
+/* tamd_dgram_frames (dgram.hip): one record per message -- where its frame header goes, the caller's
+   device address of its body (0: zeros), the body's bytes, and head = header bytes (0 or 2) << 16 |
+   the header word -- then one per datagram: where its footer goes, the footer's bytes and the
+   footer itself (dgram.h tamd_dgram_footer). */
+typedef struct DgramMsg { uint64_t dst, src; uint32_t len, head; } DgramMsg;
+typedef struct DgramFoot { uint64_t dst; uint32_t len, pad; uint8_t b[24]; } DgramFoot;
+/* tamd_dgram_sections: the caller's device address of a message section and its bytes; skip != 0:
+   not walked.  DgramOut and up to `cap` table entries out each. */
+typedef struct DgramSect { uint64_t data; uint32_t bytes, skip; } DgramSect;
+typedef struct DgramOut { uint32_t status, count, rel_off, rel_bytes; } DgramOut;
 
 static_assert(sizeof(GenDesc) == 24, "GenDesc");
 static_assert(sizeof(GatherDesc) == 12, "GatherDesc");
@@ -47,6 +57,10 @@ static_assert(sizeof(UnframeDesc) == 24, "UnframeDesc");
 static_assert(sizeof(UnframeOut) == 8, "UnframeOut");
 static_assert(sizeof(TailDesc) == 16, "TailDesc");
 static_assert(sizeof(SealDesc) == 32, "SealDesc");
+static_assert(sizeof(DgramMsg) == 24, "DgramMsg");
+static_assert(sizeof(DgramFoot) == 40, "DgramFoot");
+static_assert(sizeof(DgramSect) == 16, "DgramSect");
+static_assert(sizeof(DgramOut) == 16, "DgramOut");
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -69,6 +83,8 @@ __global__ void tamd_unframe_rows(const UnframeDesc*, uint32_t, const uint8_t*, 
 __global__ void tamd_gather_tails(const TailDesc*, uint32_t, uint8_t*);
 __global__ void tamd_seal_packets(const SealDesc*, uint32_t, const uint32_t*, uint32_t, uint32_t*);
 __global__ void tamd_gather_footers(const TailDesc*, uint32_t, uint8_t*);
+__global__ void tamd_dgram_frames(const DgramMsg*, uint32_t, const DgramFoot*, uint32_t);
+__global__ void tamd_dgram_sections(const DgramSect*, uint32_t, uint32_t, uint32_t, DgramOut*, uint32_t*);
 __global__ void tamd_timed_region();
 __global__ void tamd_nop();
 }
