@@ -77,6 +77,20 @@ def write_streams(path, streams):
                 f.write(struct.pack("<II", int(isb), len(data)) + data)
 
 
+def write_cases(path, streams):
+    """A case file of what a compressor returned, for tests/native/lz_blocks.cpp:
+    [(max, [(message, block)])], block empty when the message was sent as is."""
+    with open(path, "wb") as f:
+        f.write(b"UNLZ" + struct.pack("<I", len(streams)))
+        for max_bytes, msgs in streams:
+            f.write(struct.pack("<II", max_bytes, len(msgs)))
+            for message, block in msgs:
+                if block:
+                    f.write(struct.pack("<II", 1, len(block)) + bytes(block) + struct.pack("<iI", 0, len(message)) + message)
+                else:
+                    f.write(struct.pack("<II", 0, len(message)) + message + struct.pack("<iI", 0, 0))
+
+
 def read_cases(path, verdicts):
     """A case file of unlz_check: [(max, [(is_block, bytes, status, restored bytes)])]."""
     with open(path, "rb") as f:

@@ -1,5 +1,6 @@
 // lz_host.h -- TEST ONLY.  The host compressor of the check programs (lz_check.cpp,
-// unlz_check.cpp): a plain greedy matcher standing in for the kernel's parse, then the block as
+// unlz_check.cpp, lz_blocks.cpp): a plain greedy matcher standing in for the kernel's parse
+// (lz_host_parse), then (lz_host_write, which lz_blocks also gives the kernel's own parse) the block as
 // the kernel writes it through the host block writer of tonk_amd/csrc/lz.h: the literals as the
 // smaller of the raw and the Huffman section, the sequence tables chosen by tamd_seq_choose, the
 // backward sequence bit stream.
@@ -18,6 +19,9 @@ struct LzHostOptions {
     uint32_t floor = 0;       // a message below this many bytes is sent as is
     uint32_t len_cap = ~0u;   // match lengths and literal runs stay below this
     uint32_t max = ~0u;       // a block above the stream's maximum is not sent
+    // what lz_blocks breaks on purpose (the defaults break nothing)
+    uint32_t slack = 0;       // a block may exceed the message's length - 1 by this much
+    uint32_t win_back = 0;    // matches may start this many bytes before the window
 };
 
 struct LzHostStats {
@@ -32,12 +36,11 @@ struct LzHostStats {
     uint32_t seq_at = 0, seq_room = 0, seq_bytes = 0;
 };
 
-// Compresses the n bytes at s + pos; matches start at or after s + win (RingTrack::place).
-// `table`: the stream's hash table (1 << 14 entries, -1 when empty), updated.  Returns the block's
-// size with the block in `out`, or 0 when the message is to be sent as is.
-static inline uint32_t lz_host_block(const uint8_t* s, uint64_t pos, uint32_t n, uint64_t win, std::vector<int64_t>& table,
-                                     const uint8_t* fse, const LzHostOptions& opt, std::vector<uint8_t>* outp,
-                                     LzHostStats* st) {
+// The parse: greedy matches of the n bytes at s + pos into st->lo / st->off; matches start at or
+// after s + win (RingTrack::place).  `table`: the stream's hash table (1 << 14 entries, -1 when
+// empty), updated.
+static inline void lz_host_parse(const uint8_t* s, uint64_t pos, uint32_t n, uint64_t win, std::vector<int64_t>& table,
+                                 const LzHostOptions& opt, LzHostStats* st) {
     std::vector<uint32_t>&lo = st->lo, &off = st->off;
     auto hash = [&](uint64_t p) {
         uint32_t w;
@@ -50,7 +53,7 @@ static inline uint32_t lz_host_block(const uint8_t* s, uint64_t pos, uint32_t n,
         const int64_t c = table[hash(p)];
         table[hash(p)] = (int64_t)p;
         uint32_t len = 0;
-        if (c >= 0 && (uint64_t)c >= win && (uint64_t)c < p)
+        if (c >= 0 && (uint64_t)c + opt.win_back >= win && (uint64_t)c < p)
             while (len < n - i && len < opt.len_cap && s[c + len] == s[p + len]) ++len;
         if (len >= opt.minmatch && i - lit_start < opt.len_cap) {
             lo.push_back((i - lit_start) | (len << 16));
@@ -62,7 +65,17 @@ static inline uint32_t lz_host_block(const uint8_t* s, uint64_t pos, uint32_t n,
             ++i;
         }
     }
+}
+
+// The block of a parse (st->lo / st->off, made by lz_host_parse or read back from a block) of the
+// n bytes at msg, as the kernel writes it.  Returns the block's size with the block in `out`, or 0
+// when the message is to be sent as is.
+static inline uint32_t lz_host_write(const uint8_t* msg, uint32_t n, const uint8_t* fse, const LzHostOptions& opt,
+                                     std::vector<uint8_t>* outp, LzHostStats* st) {
+    const std::vector<uint32_t>&lo = st->lo, &off = st->off;
     if (lo.empty() || n < opt.floor) return 0;
+    uint32_t lit_start = 0;  // the end of the last match
+    for (uint32_t v : lo) lit_start += (v & 0xffffu) + (v >> 16);
     std::vector<uint8_t>& out = *outp;
     out.assign(2 * (size_t)n + 256, 0);
     uint32_t lits = n - lit_start;
@@ -73,7 +86,7 @@ static inline uint32_t lz_host_block(const uint8_t* s, uint64_t pos, uint32_t n,
     uint32_t src = 0;
     for (size_t q = 0; q <= lo.size(); ++q) {
         const uint32_t ll = q < lo.size() ? (lo[q] & 0xffffu) : n - lit_start;
-        litbuf.insert(litbuf.end(), s + pos + src, s + pos + src + ll);
+        litbuf.insert(litbuf.end(), msg + src, msg + src + ll);
         if (q < lo.size()) src += ll + (lo[q] >> 16);
     }
     uint32_t count[TAMD_HUF_SYMS] = {0};
@@ -116,11 +129,20 @@ static inline uint32_t lz_host_block(const uint8_t* s, uint64_t pos, uint32_t n,
             w += st->tt.desc_len[k];
         }
     }
-    if (w >= n - 1) return 0;
+    const uint32_t limit = n - 1 + opt.slack;  // the block stays below the message
+    if (w >= limit) return 0;
     st->seq_at = w;
-    st->seq_room = n - 1 - w;
+    st->seq_room = limit - w;
     st->seq_bytes = tamd_fse_sequences_t(lo.data(), off.data(), (uint32_t)lo.size(), fse, opt.fitted ? &st->tt : nullptr,
                                          &out[w], st->seq_room);
     w = st->seq_bytes ? w + st->seq_bytes : 0;
-    return w && w < n && w <= opt.max ? w : 0;
+    return w && w <= limit && w <= opt.max ? w : 0;
+}
+
+// Compresses the n bytes at s + pos: the parse, then its block.
+static inline uint32_t lz_host_block(const uint8_t* s, uint64_t pos, uint32_t n, uint64_t win, std::vector<int64_t>& table,
+                                     const uint8_t* fse, const LzHostOptions& opt, std::vector<uint8_t>* outp,
+                                     LzHostStats* st) {
+    lz_host_parse(s, pos, n, win, table, opt, st);
+    return lz_host_write(s + pos, n, fse, opt, outp, st);
 }

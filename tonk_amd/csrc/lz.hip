@@ -179,8 +179,10 @@ static __device__ __forceinline__ void lz_message(LzWave& L, const uint16_t* __r
         else return mb[i];
     };
     if constexpr (!BIG) {
-        // the message into LDS (16 bytes per lane per step; the slack past it is readable)
-        for (uint32_t k = 16u * lane; k < n; k += 1024) {
+        // the message into LDS (16 bytes per lane per step; the slack past it is readable), with the
+        // 8 bytes behind it: the keys of its last positions reach past its end, and what LDS held
+        // there before varies from launch to launch (the output would vary with it)
+        for (uint32_t k = 16u * lane; k < n + 8u; k += 1024) {
             const uint64_t a = lz_dword(buf, mask, m.pos + k), b = lz_dword(buf, mask, m.pos + k + 8);
             *(uint64_t*)(L.mbuf + k) = a;
             *(uint64_t*)(L.mbuf + k + 8) = b;
