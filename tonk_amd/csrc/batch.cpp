@@ -18,15 +18,9 @@
 #include "decoder.h"
 #include "device.h"
 #include "frame.h"
-#include "staging.h"
-
-#include <hip/hip_runtime.h>
+#include "handle.h"
 
 #include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-#include <stdio.h>
 
 using namespace tamd;
 
@@ -35,11 +29,9 @@ namespace {
 enum { kFrame = 0, kUnframe = 1, kTails = 2, kKinds = 3 };
 
 struct Batch {
-    std::mutex mu;
     tamd_batch_params prm;
     Device dev;
-    std::string error;
-    bool failed = false;
+    HandleCore core;  // (on dev's stream, which it does not own; destroyed before dev)
     struct Stream {
         std::unique_ptr<Context> ctx;  // (destroyed after its codecs)
         std::unique_ptr<Encoder> enc;
@@ -50,35 +42,23 @@ struct Batch {
     std::vector<Stream> st;
     std::vector<uint32_t> touched;
     uint64_t call = 0;
-    Staging desc, out;
     // index lists of a call by stream (a stable counting sort of the caller's list)
     std::vector<uint32_t> order, start;
     std::vector<RowId> rows;
-    // measurement (tamd_batch_kernel_ms)
-    bool timing = false;
-    struct Timed { int kind; hipEvent_t a, b; };
-    std::vector<Timed> timed;
-    std::vector<hipEvent_t> events;
-    double ms[kKinds] = {0, 0, 0};
-    uint64_t launches[kKinds] = {0, 0, 0}, moved[2] = {0, 0};
+    // measurement (tamd_batch_kernel_ms) beside the core's timer: bytes moved, the programs' share
+    uint64_t moved[2] = {0, 0};
     double prog_ms0 = 0;
     uint64_t prog_n0 = 0;
 
-    hipStream_t stream() const { return (hipStream_t)dev.stream(); }
+    hipStream_t stream() const { return core.stream; }
     uint32_t max_recovery() const { return prm.max_packet_bytes + TAMD_BATCH_RECOVERY_OVERHEAD; }
 
-    bool hip(hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        if (!failed) error = std::string(what) + ": " + hipGetErrorString(e);
-        failed = true;
-        return false;
-    }
     bool ok() {
-        if (!failed && dev.failed()) {
-            failed = true;
-            error = dev.error();
+        if (!core.failed && dev.failed()) {
+            core.failed = true;
+            core.error = dev.error();
         }
-        return !failed;
+        return !core.failed;
     }
     // The first use of a stream in a call: everything launched has completed, so rows freed up to
     // the stream's last closed epoch are reusable.
@@ -97,42 +77,10 @@ struct Batch {
         }
     }
 
-    hipEvent_t event() {
-        if (!events.empty()) {
-            hipEvent_t e = events.back();
-            events.pop_back();
-            return e;
-        }
-        hipEvent_t e = nullptr;
-        hip(hipEventCreate(&e), "hipEventCreate");
-        return e;
-    }
-    template <class F>
-    void launch_timed(int kind, F&& f) {
-        Timed t{kind, nullptr, nullptr};
-        if (timing) {
-            t.a = event();
-            t.b = event();
-            if (t.a) hip(hipEventRecord(t.a, stream()), "hipEventRecord");
-        }
-        f();
-        hip(hipGetLastError(), "kernel launch");
-        ++launches[kind];
-        if (timing && t.a && t.b) {
-            hip(hipEventRecord(t.b, stream()), "hipEventRecord");
-            timed.push_back(t);
-        }
-    }
     // Wait for everything enqueued; read the timed launches' durations.
     bool sync() {
         dev.synchronize();
-        for (const Timed& t : timed) {
-            float v = 0;
-            if (hipEventElapsedTime(&v, t.a, t.b) == hipSuccess) ms[t.kind] += v;
-            events.push_back(t.a);
-            events.push_back(t.b);
-        }
-        timed.clear();
+        core.timer.collect();
         return ok();
     }
 
@@ -142,12 +90,13 @@ struct Batch {
     // tamd_frame_rows over `d` (already in desc.host); enqueued only.
     void frame(size_t n, uint32_t largest) {
         if (!n || !ok()) return;
+        Staging& desc = core.desc;
         const FrameDesc* h = (const FrameDesc*)desc.host;
         for (size_t i = 0; i < n; ++i) moved[0] += h[i].len;
-        if (!hip(hipMemcpyAsync(desc.dev, desc.host, n * sizeof(FrameDesc), hipMemcpyHostToDevice, stream()), "descriptor copy"))
+        if (!core.hip(hipMemcpyAsync(desc.dev, desc.host, n * sizeof(FrameDesc), hipMemcpyHostToDevice, stream()), "descriptor copy"))
             return;
         const uint32_t wpp = waves_per_packet(largest);
-        launch_timed(kFrame, [&] {
+        core.launch_timed(kFrame, [&] {
             hipLaunchKernelGGL(tamd_frame_rows, dim3(grid(n, wpp)), dim3(256), 0, stream(), (const FrameDesc*)desc.dev,
                                (uint32_t)n, dev.arena(), wpp);
         });
@@ -156,15 +105,16 @@ struct Batch {
     // `write` only the lengths and statuses are produced.
     bool unframe(size_t n, uint64_t pitch, uint32_t largest, bool write) {
         if (!n) return sync();
-        if (!ok() || !out.ensure(n * sizeof(UnframeOut))) return hip(hipErrorOutOfMemory, "staging allocation");
-        if (!hip(hipMemcpyAsync(desc.dev, desc.host, n * sizeof(UnframeDesc), hipMemcpyHostToDevice, stream()), "descriptor copy"))
+        Staging &desc = core.desc, &out = core.out;
+        if (!ok() || !out.ensure(n * sizeof(UnframeOut))) return core.hip(hipErrorOutOfMemory, "staging allocation");
+        if (!core.hip(hipMemcpyAsync(desc.dev, desc.host, n * sizeof(UnframeDesc), hipMemcpyHostToDevice, stream()), "descriptor copy"))
             return false;
         const uint32_t wpp = write ? waves_per_packet(largest) : 1u;
-        launch_timed(kUnframe, [&] {
+        core.launch_timed(kUnframe, [&] {
             hipLaunchKernelGGL(tamd_unframe_rows, dim3(grid(n, wpp)), dim3(256), 0, stream(), (const UnframeDesc*)desc.dev,
                                (uint32_t)n, (const uint8_t*)dev.arena(), pitch, (UnframeOut*)out.dev, write ? 1u : 0u, wpp);
         });
-        hip(hipMemcpyAsync(out.host, out.dev, n * sizeof(UnframeOut), hipMemcpyDeviceToHost, stream()), "result copy");
+        core.hip(hipMemcpyAsync(out.host, out.dev, n * sizeof(UnframeOut), hipMemcpyDeviceToHost, stream()), "result copy");
         if (!sync()) return false;
         const UnframeOut* o = (const UnframeOut*)out.host;
         for (size_t i = 0; i < n && write; ++i) moved[1] += o[i].len;
@@ -210,12 +160,21 @@ struct Batch {
             }
         return true;
     }
+    // The rows of a stretch of k packets of one stream; without them the codec is disabled (an
+    // arena range that is full disables it, as in the C ABI).
+    template <class Codec>
+    bool stretch_rows(Codec& codec, Context& c, uint32_t k, uint32_t bytes) {
+        if (!codec.disabled() && alloc_rows(c, k, bytes)) return true;
+        codec.set_disabled();
+        return false;
+    }
+    bool staging_failed() { return core.hip(hipErrorOutOfMemory, "staging allocation"); }
 };
 
 // Common entry checks; returns 0 with the handle locked by `lk`.
 int enter(Batch* b, std::unique_lock<std::mutex>& lk, uint32_t n, const uint32_t* stream) {
     if (!b) return -1;
-    lk = std::unique_lock<std::mutex>(b->mu);
+    lk = std::unique_lock<std::mutex>(b->core.mu);
     if (!b->ok()) return -4;
     for (uint32_t i = 0; i < n; ++i)
         if (stream[i] >= b->prm.n_streams) return -2;
@@ -224,26 +183,62 @@ int enter(Batch* b, std::unique_lock<std::mutex>& lk, uint32_t n, const uint32_t
     return 0;
 }
 
+// What the two add calls share: packet i of the list is len[i] bytes at dev_payloads + i * pitch +
+// offset[i] (a null offset: 0).  The list is walked stream by stream in list order; `stretch(s, x,
+// idx, m, took)` is given what is left of stream s's entries (idx[0 .. m)), adds a stretch of them
+// from the first, sets their result codes, calls took(i, row) for every packet i that a row took,
+// and returns how many entries they were.  The packets taken are framed into their rows by one
+// launch.
+template <class F>
+int add_packets(Batch* b, uint32_t n, const uint32_t* stream, const uint32_t* len, const uint32_t* offset, const void* dev_payloads,
+                uint64_t pitch, F&& stretch) {
+    std::unique_lock<std::mutex> lk;
+    if (const int e = enter(b, lk, n, stream)) return e;
+    const uint32_t maxb = b->prm.max_packet_bytes;
+    uint32_t largest = 0;
+    for (uint32_t i = 0; i < n; ++i) {
+        if (len[i] > maxb) continue;
+        if (len[i] > largest) largest = len[i];
+        if (len[i] && (uint64_t)(offset ? offset[i] : 0u) + len[i] > pitch) return -3;
+    }
+    if (!b->core.desc.ensure((size_t)n * sizeof(FrameDesc))) return b->staging_failed(), -4;
+    FrameDesc* d = (FrameDesc*)b->core.desc.host;
+    size_t nd = 0;
+    b->sort_by_stream(n, stream);
+    for (uint32_t s = 0; s < b->prm.n_streams; ++s) {
+        const uint32_t* idx = b->order.data() + b->start[s];
+        const uint32_t m = b->start[s + 1] - b->start[s];
+        if (!m) continue;
+        Batch::Stream& x = b->use(s);
+        const RowTable& pool = x.ctx->rows;
+        const auto took = [&](uint32_t i, RowId r) {
+            d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_payloads + (uint64_t)i * pitch + (offset ? offset[i] : 0u), pool.offset(r),
+                                len[i], pool.cap_bytes(r), 0};
+        };
+        for (uint32_t a = 0; a < m;) a += stretch(s, x, idx + a, m - a, took);
+    }
+    b->frame(nd, largest + 3);
+    return b->sync() ? 0 : -4;
+}
+
 }  // namespace
 
 extern "C" {
 
 void* tamd_batch_create(const tamd_batch_params* p, char* err, size_t err_len) {
-    auto fail = [&](const std::string& m) -> void* {
-        if (err && err_len) snprintf(err, err_len, "%s", m.c_str());
-        return nullptr;
-    };
     if (!p || p->n_streams == 0 || p->max_packet_bytes == 0 || p->max_packet_bytes > 65535 || p->arena_bytes == 0)
-        return fail("bad parameters");
+        return fail(err, err_len, "bad parameters");
     const uint64_t range = (p->arena_bytes / p->n_streams) & ~(uint64_t)(TAMD_ROW_UNIT - 1);
-    if (range < 64u * (p->max_packet_bytes + 64u)) return fail("bad parameters: arena too small for the streams");
-    if (!gf_init()) return fail("gf self test failed");
+    if (range < 64u * (p->max_packet_bytes + 64u)) return fail(err, err_len, "bad parameters: arena too small for the streams");
+    if (!gf_init()) return fail(err, err_len, "gf self test failed");
     std::unique_ptr<Batch> b(new Batch());
     b->prm = *p;
     b->dev.set_small_uploads(p->n_streams <= 4);
     b->dev.set_program_slots(2, 4u << 20);
-    if (!b->dev.init((int)p->device, p->arena_bytes)) return fail(b->dev.error());
-    if (!b->dev.gf_selftest()) return fail("device GF(256) self test failed");
+    if (!b->dev.init((int)p->device, p->arena_bytes)) return fail(err, err_len, b->dev.error());
+    b->core.device = b->dev.device();
+    b->core.stream = (hipStream_t)b->dev.stream();
+    if (!b->dev.gf_selftest()) return fail(err, err_len, "device GF(256) self test failed");
     const uint32_t row_cap = (p->max_packet_bytes + TAMD_BATCH_RECOVERY_OVERHEAD + 63u) / 64u * 64u;
     b->st.resize(p->n_streams);
     for (uint32_t i = 0; i < p->n_streams; ++i) {
@@ -264,18 +259,14 @@ void tamd_batch_destroy(void* h) {
     Batch* b = (Batch*)h;
     if (!b) return;
     {
-        std::lock_guard<std::mutex> lk(b->mu);
+        std::lock_guard<std::mutex> lk(b->core.mu);
         b->dev.bind_thread();
         b->dev.synchronize();
-        for (hipEvent_t e : b->events) hipEventDestroy(e);
     }
     delete b;
 }
 
-const char* tamd_batch_error(void* h) {
-    Batch* b = (Batch*)h;
-    return b ? b->error.c_str() : "bad handle";
-}
+const char* tamd_batch_error(void* h) { return error_text<Batch>(h); }
 
 int tamd_batch_encoder_add(void* h, uint32_t n, const uint32_t* stream, const uint32_t* len, const void* dev_payloads,
                            uint64_t pitch, uint32_t* packet_num, int32_t* rc) {
@@ -287,57 +278,31 @@ int tamd_batch_encoder_add_at(void* h, uint32_t n, const uint32_t* stream, const
                               const void* dev_payloads, uint64_t pitch, uint32_t* packet_num, int32_t* rc) {
     Batch* b = (Batch*)h;
     if (!b || !stream || !len || !dev_payloads || !packet_num || !rc) return -1;
-    std::unique_lock<std::mutex> lk;
-    if (const int e = enter(b, lk, n, stream)) return e;
-    const uint32_t maxb = b->prm.max_packet_bytes;
-    uint32_t largest = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (len[i] > maxb) continue;
-        if (len[i] > largest) largest = len[i];
-        if (len[i] && (uint64_t)(offset ? offset[i] : 0u) + len[i] > pitch) return -3;
-    }
-    if (!b->desc.ensure((size_t)n * sizeof(FrameDesc))) return b->hip(hipErrorOutOfMemory, "staging allocation"), -4;
-    FrameDesc* d = (FrameDesc*)b->desc.host;
-    size_t nd = 0;
-    b->sort_by_stream(n, stream);
-    for (uint32_t s = 0; s < b->prm.n_streams; ++s) {
-        const uint32_t* idx = b->order.data() + b->start[s];
-        const uint32_t m = b->start[s + 1] - b->start[s];
-        if (!m) continue;
-        Batch::Stream& x = b->use(s);
-        Context& c = *x.ctx;
-        for (uint32_t a = 0; a < m;) {
-            const uint32_t i0 = idx[a], l = len[i0];
-            packet_num[i0] = 0;
-            if (l == 0 || l > maxb) { rc[i0] = kInvalidInput; ++a; continue; }
-            uint32_t k = 1;  // the stretch of equally long packets from here
-            while (a + k < m && len[idx[a + k]] == l) ++k;
-            const uint32_t hb = length_header_bytes(l), framed = hb + l;
-            const bool have = !x.enc->disabled() && b->alloc_rows(c, k, framed);
-            if (!have) {  // (an arena range that is full disables the codec, as in the C ABI)
-                x.enc->set_disabled();
-                for (uint32_t j = 0; j < k; ++j) { rc[idx[a + j]] = kDisabled; packet_num[idx[a + j]] = 0; }
-                a += k;
-                continue;
-            }
-            uint32_t col0 = 0;
-            const bool run = k >= 2 && x.enc->add_run(b->rows.data(), k, framed, hb, l, false, &col0);
-            for (uint32_t j = 0; j < k; ++j) {
-                const uint32_t i = idx[a + j];
-                const RowId r = b->rows[j];
-                uint32_t pn = col_add(col0, j);
-                const Result res = run ? kSuccess : x.enc->add(r, framed, hb, l, nullptr, &pn, false);
-                rc[i] = res;
-                packet_num[i] = res == kSuccess ? pn : 0;
-                if (res != kSuccess) { c.rows.free_deferred(r); continue; }
-                d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_payloads + (uint64_t)i * pitch + (offset ? offset[i] : 0u),
-                                    c.rows.offset(r), l, c.rows.cap_bytes(r), 0};
-            }
-            a += k;
+    return add_packets(b, n, stream, len, offset, dev_payloads, pitch,
+                       [&](uint32_t, Batch::Stream& x, const uint32_t* idx, uint32_t m, const auto& took) {
+        const uint32_t l = len[idx[0]];
+        packet_num[idx[0]] = 0;
+        if (l == 0 || l > b->prm.max_packet_bytes) return rc[idx[0]] = kInvalidInput, 1u;
+        uint32_t k = 1;  // the stretch of equally long packets from here
+        while (k < m && len[idx[k]] == l) ++k;
+        const uint32_t hb = length_header_bytes(l), framed = hb + l;
+        if (!b->stretch_rows(*x.enc, *x.ctx, k, framed)) {
+            for (uint32_t j = 0; j < k; ++j) { rc[idx[j]] = kDisabled; packet_num[idx[j]] = 0; }
+            return k;
         }
-    }
-    b->frame(nd, largest + 3);
-    return b->sync() ? 0 : -4;
+        uint32_t col0 = 0;
+        const bool run = k >= 2 && x.enc->add_run(b->rows.data(), k, framed, hb, l, false, &col0);
+        for (uint32_t j = 0; j < k; ++j) {
+            const RowId r = b->rows[j];
+            uint32_t pn = col_add(col0, j);
+            const Result res = run ? kSuccess : x.enc->add(r, framed, hb, l, nullptr, &pn, false);
+            rc[idx[j]] = res;
+            packet_num[idx[j]] = res == kSuccess ? pn : 0;
+            if (res == kSuccess) took(idx[j], r);
+            else x.ctx->rows.free_deferred(r);
+        }
+        return k;
+    });
 }
 
 int tamd_batch_encode(void* h, uint32_t n, const uint32_t* stream, void* dev_out, uint64_t pitch, uint32_t* bytes,
@@ -347,8 +312,8 @@ int tamd_batch_encode(void* h, uint32_t n, const uint32_t* stream, void* dev_out
     std::unique_lock<std::mutex> lk;
     if (const int e = enter(b, lk, n, stream)) return e;
     if (pitch < b->max_recovery()) return -3;
-    if (!b->desc.ensure((size_t)n * sizeof(UnframeDesc))) return b->hip(hipErrorOutOfMemory, "staging allocation"), -4;
-    UnframeDesc* d = (UnframeDesc*)b->desc.host;
+    if (!b->core.desc.ensure((size_t)n * sizeof(UnframeDesc))) return b->staging_failed(), -4;
+    UnframeDesc* d = (UnframeDesc*)b->core.desc.host;
     size_t nd = 0;
     std::vector<std::pair<uint32_t, RowId>> made;
     uint32_t largest = 0;
@@ -396,55 +361,28 @@ int tamd_batch_decoder_add_original_at(void* h, uint32_t n, const uint32_t* stre
                                        int32_t* rc) {
     Batch* b = (Batch*)h;
     if (!b || !stream || !packet_num || !len || !dev_payloads || !rc) return -1;
-    std::unique_lock<std::mutex> lk;
-    if (const int e = enter(b, lk, n, stream)) return e;
-    const uint32_t maxb = b->prm.max_packet_bytes;
-    uint32_t largest = 0;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (len[i] > maxb) continue;
-        if (len[i] > largest) largest = len[i];
-        if (len[i] && (uint64_t)(offset ? offset[i] : 0u) + len[i] > pitch) return -3;
-    }
-    if (!b->desc.ensure((size_t)n * sizeof(FrameDesc))) return b->hip(hipErrorOutOfMemory, "staging allocation"), -4;
-    FrameDesc* d = (FrameDesc*)b->desc.host;
-    size_t nd = 0;
-    b->sort_by_stream(n, stream);
-    for (uint32_t s = 0; s < b->prm.n_streams; ++s) {
-        const uint32_t* idx = b->order.data() + b->start[s];
-        const uint32_t m = b->start[s + 1] - b->start[s];
-        if (!m) continue;
-        Batch::Stream& x = b->use(s);
-        Context& c = *x.ctx;
+    return add_packets(b, n, stream, len, offset, dev_payloads, pitch,
+                       [&](uint32_t s, Batch::Stream& x, const uint32_t* idx, uint32_t m, const auto& took) {
+        const uint32_t l = len[idx[0]], pn0 = packet_num[idx[0]];
         b->touch(s);  // (an original that completes a region may recover packets: ops pending)
-        for (uint32_t a = 0; a < m;) {
-            const uint32_t i0 = idx[a], l = len[i0], pn0 = packet_num[i0];
-            if (l == 0 || l > maxb || pn0 >= kColumnPeriod) { rc[i0] = kInvalidInput; ++a; continue; }
-            uint32_t k = 1;  // the stretch of equally long packets with consecutive numbers from here
-            while (a + k < m && len[idx[a + k]] == l && packet_num[idx[a + k]] == pn0 + k && pn0 + k < kColumnPeriod) ++k;
-            const uint32_t hb = length_header_bytes(l), framed = hb + l;
-            const bool have = !x.dec->disabled() && b->alloc_rows(c, k, framed);
-            if (!have) {
-                x.dec->set_disabled();
-                for (uint32_t j = 0; j < k; ++j) rc[idx[a + j]] = kDisabled;
-                a += k;
-                continue;
-            }
-            const bool run = k >= 2 && x.dec->add_run_inorder(pn0, b->rows.data(), k, framed, hb, l, false);
-            for (uint32_t j = 0; j < k; ++j) {
-                const uint32_t i = idx[a + j];
-                const RowId r = b->rows[j];
-                bool took = run;
-                const Result res = run ? kSuccess : x.dec->add_original(pn0 + j, r, framed, hb, l, nullptr, &took, false);
-                rc[i] = res;
-                if (!took) { c.rows.free_deferred(r); continue; }
-                d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_payloads + (uint64_t)i * pitch + (offset ? offset[i] : 0u),
-                                    c.rows.offset(r), l, c.rows.cap_bytes(r), 0};
-            }
-            a += k;
+        if (l == 0 || l > b->prm.max_packet_bytes || pn0 >= kColumnPeriod) return rc[idx[0]] = kInvalidInput, 1u;
+        uint32_t k = 1;  // the stretch of equally long packets with consecutive numbers from here
+        while (k < m && len[idx[k]] == l && packet_num[idx[k]] == pn0 + k && pn0 + k < kColumnPeriod) ++k;
+        const uint32_t hb = length_header_bytes(l), framed = hb + l;
+        if (!b->stretch_rows(*x.dec, *x.ctx, k, framed)) {
+            for (uint32_t j = 0; j < k; ++j) rc[idx[j]] = kDisabled;
+            return k;
         }
-    }
-    b->frame(nd, largest + 3);
-    return b->sync() ? 0 : -4;
+        const bool run = k >= 2 && x.dec->add_run_inorder(pn0, b->rows.data(), k, framed, hb, l, false);
+        for (uint32_t j = 0; j < k; ++j) {
+            const RowId r = b->rows[j];
+            bool kept = run;
+            rc[idx[j]] = run ? kSuccess : x.dec->add_original(pn0 + j, r, framed, hb, l, nullptr, &kept, false);
+            if (kept) took(idx[j], r);
+            else x.ctx->rows.free_deferred(r);
+        }
+        return k;
+    });
 }
 
 int tamd_batch_decoder_add_recovery(void* h, uint32_t n, const uint32_t* stream, const uint32_t* bytes,
@@ -453,44 +391,41 @@ int tamd_batch_decoder_add_recovery(void* h, uint32_t n, const uint32_t* stream,
     if (!b || !stream || !bytes || !dev_packets || !rc) return -1;
     std::unique_lock<std::mutex> lk;
     if (const int e = enter(b, lk, n, stream)) return e;
-    const uint32_t maxb = b->max_recovery();
-    uint32_t largest = 0;
-    for (uint32_t i = 0; i < n; ++i)
-        if (bytes[i] <= maxb && bytes[i] > largest) largest = bytes[i];
+    const uint32_t maxb = b->max_recovery(), largest = largest_within(bytes, n, maxb);
     if (pitch < largest) return -3;
     if (!n) return 0;
     // the packets' last bytes (their footers): one gather, one copy
+    HandleCore& c = b->core;
     const size_t desc_bytes = (size_t)n * (sizeof(FrameDesc) > sizeof(TailDesc) ? sizeof(FrameDesc) : sizeof(TailDesc));
-    if (!b->desc.ensure(desc_bytes) || !b->out.ensure((size_t)n * 8)) return b->hip(hipErrorOutOfMemory, "staging allocation"), -4;
-    TailDesc* t = (TailDesc*)b->desc.host;
+    if (!c.room(desc_bytes, (size_t)n * 8)) return -4;
+    TailDesc* t = (TailDesc*)c.desc.host;
     for (uint32_t i = 0; i < n; ++i) {
         const bool valid = bytes[i] >= 1 && bytes[i] <= maxb;
         t[i] = TailDesc{(uint64_t)(uintptr_t)dev_packets + (uint64_t)i * pitch, valid ? bytes[i] : 0u, 0};
     }
-    b->hip(hipMemcpyAsync(b->desc.dev, b->desc.host, (size_t)n * sizeof(TailDesc), hipMemcpyHostToDevice, b->stream()), "descriptor copy");
+    c.hip(hipMemcpyAsync(c.desc.dev, c.desc.host, (size_t)n * sizeof(TailDesc), hipMemcpyHostToDevice, c.stream), "descriptor copy");
     if (b->ok())
-        b->launch_timed(kTails, [&] {
-            hipLaunchKernelGGL(tamd_gather_tails, dim3((n + 255) / 256), dim3(256), 0, b->stream(), (const TailDesc*)b->desc.dev, n,
-                               b->out.dev);
+        c.launch_timed(kTails, [&] {
+            hipLaunchKernelGGL(tamd_gather_tails, dim3((n + 255) / 256), dim3(256), 0, c.stream, (const TailDesc*)c.desc.dev, n, c.out.dev);
         });
-    b->hip(hipMemcpyAsync(b->out.host, b->out.dev, (size_t)n * 8, hipMemcpyDeviceToHost, b->stream()), "tail copy");
+    c.hip(hipMemcpyAsync(c.out.host, c.out.dev, (size_t)n * 8, hipMemcpyDeviceToHost, c.stream), "tail copy");
     if (!b->sync()) return -4;
-    const uint8_t* tails = b->out.host;
-    FrameDesc* d = (FrameDesc*)b->desc.host;  // (the tail records are done with)
+    const uint8_t* tails = c.out.host;
+    FrameDesc* d = (FrameDesc*)c.desc.host;  // (the tail records are done with)
     size_t nd = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t s = stream[i], total = bytes[i];
         if (total < 1 || total > maxb) { rc[i] = kInvalidInput; continue; }
         Batch::Stream& x = b->use(s);
-        Context& c = *x.ctx;
+        Context& cx = *x.ctx;
         if (x.dec->disabled()) { rc[i] = kDisabled; continue; }
-        const RowId r = c.alloc(total);
+        const RowId r = cx.alloc(total);
         if (r == kNoRow) { x.dec->set_disabled(); rc[i] = kDisabled; continue; }
         bool took = false;
         b->touch(s);
         rc[i] = x.dec->add_recovery(r, total, tails + (size_t)i * 8, nullptr, &took);
-        if (!took) { c.rows.free_deferred(r); continue; }
-        d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_packets + (uint64_t)i * pitch, c.rows.offset(r), total, c.rows.cap_bytes(r), 1};
+        if (!took) { cx.rows.free_deferred(r); continue; }
+        d[nd++] = FrameDesc{(uint64_t)(uintptr_t)dev_packets + (uint64_t)i * pitch, cx.rows.offset(r), total, cx.rows.cap_bytes(r), 1};
     }
     b->frame(nd, largest);
     return b->sync() ? 0 : -4;
@@ -528,18 +463,18 @@ int tamd_batch_decode(void* h, uint32_t n, const uint32_t* stream, void* dev_out
     // disabled and its packets leave the list (capi.cpp read_back's rule): none of its bytes are
     // written, and the other streams' packets land at their final slots.
     for (int pass = 0; pass < 2 && !got.empty(); ++pass) {
-        if (!b->desc.ensure(got.size() * sizeof(UnframeDesc))) return b->hip(hipErrorOutOfMemory, "staging allocation"), -4;
-        UnframeDesc* d = (UnframeDesc*)b->desc.host;
+        if (!b->core.desc.ensure(got.size() * sizeof(UnframeDesc))) return b->staging_failed(), -4;
+        UnframeDesc* d = (UnframeDesc*)b->core.desc.host;
         uint32_t largest = 0;
         for (size_t j = 0; j < got.size(); ++j) {
             d[j] = UnframeDesc{(uint64_t)(uintptr_t)dev_out + (uint64_t)j * pitch, got[j].row_units, got[j].upper, 0, 0};
             if (got[j].upper > largest) largest = got[j].upper;
         }
         if (!b->unframe(got.size(), pitch, largest, pass == 1)) return -4;
-        const UnframeOut* o = (const UnframeOut*)b->out.host;
+        const UnframeOut* o = (const UnframeOut*)b->core.out.host;
         if (pass == 1) {  // (the rows the first launch accepted, unchanged since)
             for (size_t j = 0; j < got.size(); ++j)
-                if (o[j].status != TAMD_FRAME_OK || o[j].len != out_bytes[j]) return b->hip(hipErrorUnknown, "recovered row changed"), -4;
+                if (o[j].status != TAMD_FRAME_OK || o[j].len != out_bytes[j]) return b->core.hip(hipErrorUnknown, "recovered row changed"), -4;
             break;
         }
         for (size_t j = 0; j < got.size(); ++j)
@@ -580,24 +515,25 @@ int tamd_batch_decoder_ack(void* h, uint32_t stream, uint8_t* buffer, uint32_t l
 void tamd_batch_set_timing(void* h, int on) {
     Batch* b = (Batch*)h;
     if (!b) return;
-    std::lock_guard<std::mutex> lk(b->mu);
+    std::lock_guard<std::mutex> lk(b->core.mu);
     b->dev.bind_thread();
-    b->timing = on != 0;
+    b->core.timer.on = on != 0;
     b->dev.set_timing(on != 0);
 }
 
 void tamd_batch_kernel_ms(void* h, double* out, unsigned n) {
     Batch* b = (Batch*)h;
     if (!b || !out) return;
-    std::lock_guard<std::mutex> lk(b->mu);
+    std::lock_guard<std::mutex> lk(b->core.mu);
     b->dev.bind_thread();
     b->dev.collect_timing();
     DeviceStats& ds = b->dev.stats();
-    const double v[10] = {b->ms[kFrame], b->ms[kUnframe], b->ms[kTails], ds.kernel_ms - b->prog_ms0,
-                          (double)b->launches[kFrame], (double)b->launches[kUnframe], (double)b->launches[kTails],
+    LaunchTimer& t = b->core.timer;
+    const double v[10] = {t.ms[kFrame], t.ms[kUnframe], t.ms[kTails], ds.kernel_ms - b->prog_ms0,
+                          (double)t.launches[kFrame], (double)t.launches[kUnframe], (double)t.launches[kTails],
                           (double)(ds.timed_launches - b->prog_n0), (double)b->moved[0], (double)b->moved[1]};
     for (unsigned i = 0; i < n && i < 10; ++i) out[i] = v[i];
-    for (int k = 0; k < kKinds; ++k) { b->ms[k] = 0; b->launches[k] = 0; }
+    t.reset();
     b->moved[0] = b->moved[1] = 0;
     b->prog_ms0 = ds.kernel_ms;
     b->prog_n0 = ds.timed_launches;

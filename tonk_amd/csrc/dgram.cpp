@@ -1,23 +1,16 @@
 // dgram.cpp -- include/tonk_datagram.h: batched building and parsing of datagrams in the caller's
-// device memory.  A handle holds pinned descriptor and result staging and one stream; it has no
-// per-connection state.  Every call is one descriptor copy, one launch of a kernel of dgram.hip,
-// one result copy (parse) and one wait.  The layout of a datagram -- every message's offset, the
-// spans, the footer's bytes -- is computed here from lengths the caller gave (dgram.h
-// tamd_dgram_layout, tamd_dgram_footer); the device moves the bytes.
+// device memory.  A handle is the shared core (handle.h: lock, stream, pinned descriptor and result
+// staging); it has no per-connection state.  Every call is one descriptor copy, one launch of a
+// kernel of dgram.hip, one result copy (parse) and one wait.  The layout of a datagram -- every
+// message's offset, the spans, the footer's bytes -- is computed here from lengths the caller gave
+// (dgram.h tamd_dgram_layout, tamd_dgram_footer); the device moves the bytes.
 #include "../../include/tonk_datagram.h"
 
 #include "dgram.h"
+#include "handle.h"
 #include "kernel_abi.h"
-#include "staging.h"
-
-#include <hip/hip_runtime.h>
 
 #include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-#include <stdio.h>
-#include <string.h>
 
 using namespace tamd;
 
@@ -26,105 +19,30 @@ namespace {
 enum { kBuild = 0, kParse = 1, kKinds = 2 };
 
 struct Framer {
-    std::mutex mu;
+    HandleCore core;
     tamd_dgram_params prm;
-    int device = -1;
-    hipStream_t st = nullptr;
-    std::string error;
-    bool failed = false;
-    Staging desc, out;
     std::vector<uint32_t> offs;  // a call's message offsets
-    bool timing = false;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    double ms[kKinds] = {0, 0};
-    uint64_t launches[kKinds] = {0, 0};
-
-    bool hip(hipError_t e, const char* what) {
-        if (e == hipSuccess) return true;
-        if (!failed) error = std::string(what) + ": " + hipGetErrorString(e);
-        failed = true;
-        return false;
-    }
-
-    bool room(size_t up, size_t down) {
-        if (desc.ensure(up) && out.ensure(down)) return true;
-        return hip(hipErrorOutOfMemory, "staging allocation");
-    }
-
-    // Upload `up` descriptor bytes, run `launch`, bring `down` result bytes back and wait.
-    template <class F>
-    bool run(int kind, size_t up, size_t down, F&& launch) {
-        if (!hip(hipMemcpyAsync(desc.dev, desc.host, up, hipMemcpyHostToDevice, st), "descriptor copy")) return false;
-        const bool timed = timing && ev[0] && ev[1];
-        if (timed) hip(hipEventRecord(ev[0], st), "hipEventRecord");
-        launch();
-        hip(hipGetLastError(), "kernel launch");
-        if (timed) hip(hipEventRecord(ev[1], st), "hipEventRecord");
-        ++launches[kind];
-        if (down) hip(hipMemcpyAsync(out.host, out.dev, down, hipMemcpyDeviceToHost, st), "result copy");
-        hip(hipStreamSynchronize(st), "hipStreamSynchronize");
-        float v = 0;
-        if (timed && !failed && hipEventElapsedTime(&v, ev[0], ev[1]) == hipSuccess) ms[kind] += v;
-        return !failed;
-    }
-
-    ~Framer() {
-        if (device < 0) return;
-        hipSetDevice(device);
-        if (st) hipStreamSynchronize(st);
-        for (hipEvent_t e : ev)
-            if (e) hipEventDestroy(e);
-        desc.release();
-        out.release();
-        if (st) hipStreamDestroy(st);
-    }
 };
-
-// Common entry checks; returns 0 with the handle locked by `lk` and its device current.
-int enter(Framer* s, std::unique_lock<std::mutex>& lk) {
-    if (!s) return -1;
-    lk = std::unique_lock<std::mutex>(s->mu);
-    if (s->failed) return -4;
-    hipSetDevice(s->device);
-    return 0;
-}
 
 }  // namespace
 
 extern "C" {
 
 void* tamd_dgram_create(const tamd_dgram_params* p, char* err, size_t err_len) {
-    auto fail = [&](const std::string& m) -> void* {
-        if (err && err_len) snprintf(err, err_len, "%s", m.c_str());
-        return nullptr;
-    };
-    if (!p || p->max_datagram_bytes < 8 || p->max_datagram_bytes > 65535) return fail("bad parameters");
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n < 0 || (uint32_t)n <= p->device)
-        return fail("tonk_amd: no HIP device available (datagrams are built and parsed only on MI355X/gfx950)");
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, (int)p->device) != hipSuccess) return fail("hipGetDeviceProperties failed");
-    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(std::string("tonk_amd: device is ") + prop.gcnArchName + ", kernels are built for gfx950");
+    if (!p || p->max_datagram_bytes < 8 || p->max_datagram_bytes > 65535) return fail(err, err_len, "bad parameters");
+    std::string why = device_check(p->device, "datagrams are built and parsed");
+    if (!why.empty()) return fail(err, err_len, why);
     std::unique_ptr<Framer> s(new Framer());
     s->prm = *p;
-    if (hipSetDevice((int)p->device) != hipSuccess) return fail("hipSetDevice failed");
-    s->device = (int)p->device;
-    if (hipStreamCreateWithFlags(&s->st, hipStreamNonBlocking) != hipSuccess) return fail("tonk_amd: the stream could not be created");
+    why = s->core.open(p->device);
+    if (!why.empty()) return fail(err, err_len, why);
     return s.release();
 }
 
-void tamd_dgram_destroy(void* h) {
-    Framer* s = (Framer*)h;
-    if (!s) return;
-    { std::lock_guard<std::mutex> lk(s->mu); }
-    delete s;
-}
-
-const char* tamd_dgram_error(void* h) {
-    Framer* s = (Framer*)h;
-    return s ? s->error.c_str() : "bad handle";
-}
+void tamd_dgram_destroy(void* h) { destroy<Framer>(h); }
+const char* tamd_dgram_error(void* h) { return error_text<Framer>(h); }
+void tamd_dgram_set_timing(void* h, int on) { set_timing<Framer>(h, on); }
+void tamd_dgram_kernel_ms(void* h, double* out, unsigned n) { kernel_ms<Framer>(h, out, n, kKinds); }
 
 int tamd_dgram_build(void* h, uint32_t n, uint32_t m, const uint32_t* dgram, const uint32_t* type, const uint32_t* bytes,
                      const uint64_t* src, const uint32_t* seq, const uint32_t* seq_bytes, const uint32_t* nonce,
@@ -139,15 +57,16 @@ int tamd_dgram_build(void* h, uint32_t n, uint32_t m, const uint32_t* dgram, con
         return -1;
     std::unique_lock<std::mutex> lk;
     if (const int e = enter(s, lk)) return e;
+    HandleCore& c = s->core;
     for (uint32_t j = 0; j < m; ++j)
         if (dgram[j] >= n || (j && dgram[j] < dgram[j - 1])) return -2;
     if (pitch < tamd_dgram_footer_bytes(0, 0, 0)) return -3;
     if (!n) return 0;
-    if (!s->room((size_t)m * sizeof(DgramMsg) + (size_t)n * sizeof(DgramFoot), 0)) return -4;
+    if (!c.room((size_t)m * sizeof(DgramMsg) + (size_t)n * sizeof(DgramFoot), 0)) return -4;
     s->offs.resize(m ? m : 1u);
     // (the footers start where the longest possible message list ends: 24 m is a multiple of 8)
-    DgramMsg* dm = (DgramMsg*)s->desc.host;
-    DgramFoot* df = (DgramFoot*)(s->desc.host + (size_t)m * sizeof(DgramMsg));
+    DgramMsg* dm = (DgramMsg*)c.desc.host;
+    DgramFoot* df = (DgramFoot*)(c.desc.host + (size_t)m * sizeof(DgramMsg));
     uint32_t nm = 0, nf = 0, j = 0;
     for (uint32_t i = 0; i < n; ++i) {
         const uint32_t j0 = j;
@@ -175,13 +94,13 @@ int tamd_dgram_build(void* h, uint32_t n, uint32_t m, const uint32_t* dgram, con
     }
     if (!nf) return 0;
     // (the records of refused datagrams are left out: the footers move up behind the messages kept)
-    DgramFoot* packed = (DgramFoot*)(s->desc.host + (size_t)nm * sizeof(DgramMsg));
+    DgramFoot* packed = (DgramFoot*)(c.desc.host + (size_t)nm * sizeof(DgramMsg));
     if (packed != df) memmove(packed, df, (size_t)nf * sizeof(DgramFoot));
     const size_t up = (size_t)nm * sizeof(DgramMsg) + (size_t)nf * sizeof(DgramFoot);
     const uint32_t per_block = 256u / 16u, blocks = (nm + nf + per_block - 1u) / per_block;
-    const bool ok = s->run(kBuild, up, 0, [&] {
-        hipLaunchKernelGGL(tamd_dgram_frames, dim3(blocks), dim3(256), 0, s->st, (const DgramMsg*)s->desc.dev, nm,
-                           (const DgramFoot*)(s->desc.dev + (size_t)nm * sizeof(DgramMsg)), nf);
+    const bool ok = c.run(kBuild, up, 0, [&] {
+        hipLaunchKernelGGL(tamd_dgram_frames, dim3(blocks), dim3(256), 0, c.stream, (const DgramMsg*)c.desc.dev, nm,
+                           (const DgramFoot*)(c.desc.dev + (size_t)nm * sizeof(DgramMsg)), nf);
     });
     return ok ? 0 : -4;
 }
@@ -194,22 +113,23 @@ int tamd_dgram_parse(void* h, uint32_t n, const uint32_t* bytes, const uint32_t*
         return -1;
     std::unique_lock<std::mutex> lk;
     if (const int e = enter(s, lk)) return e;
+    HandleCore& c = s->core;
     const uint32_t maxb = s->prm.max_datagram_bytes;
     for (uint32_t i = 0; i < n; ++i)
         if (bytes[i] <= maxb && (uint64_t)(offset ? offset[i] : 0u) + bytes[i] > pitch) return -3;
     if (!n) return 0;
     const size_t heads = (size_t)n * sizeof(DgramOut), down = heads + (size_t)n * cap * sizeof(uint32_t);
-    if (!s->room((size_t)n * sizeof(DgramSect), down)) return -4;
-    DgramSect* d = (DgramSect*)s->desc.host;
+    if (!c.room((size_t)n * sizeof(DgramSect), down)) return -4;
+    DgramSect* d = (DgramSect*)c.desc.host;
     for (uint32_t i = 0; i < n; ++i)
         d[i] = DgramSect{(uint64_t)(uintptr_t)dev + (uint64_t)i * pitch + (offset ? offset[i] : 0u), bytes[i], bytes[i] <= maxb ? 0u : 1u};
-    const bool ok = s->run(kParse, (size_t)n * sizeof(DgramSect), down, [&] {
-        hipLaunchKernelGGL(tamd_dgram_sections, dim3((n + 63u) / 64u), dim3(512), 0, s->st, (const DgramSect*)s->desc.dev, n, mode, cap,
-                           (DgramOut*)s->out.dev, (uint32_t*)(s->out.dev + heads));
+    const bool ok = c.run(kParse, (size_t)n * sizeof(DgramSect), down, [&] {
+        hipLaunchKernelGGL(tamd_dgram_sections, dim3((n + 63u) / 64u), dim3(512), 0, c.stream, (const DgramSect*)c.desc.dev, n, mode, cap,
+                           (DgramOut*)c.out.dev, (uint32_t*)(c.out.dev + heads));
     });
     if (!ok) return -4;
-    const DgramOut* o = (const DgramOut*)s->out.host;
-    const uint32_t* t = (const uint32_t*)(s->out.host + heads);
+    const DgramOut* o = (const DgramOut*)c.out.host;
+    const uint32_t* t = (const uint32_t*)(c.out.host + heads);
     for (uint32_t i = 0; i < n; ++i) {
         const bool skipped = bytes[i] > maxb;
         status[i] = skipped ? 1u : o[i].status;
@@ -220,25 +140,6 @@ int tamd_dgram_parse(void* h, uint32_t n, const uint32_t* bytes, const uint32_t*
         if (kept) memcpy(table + (size_t)i * cap, t + (size_t)i * cap, (size_t)kept * sizeof(uint32_t));
     }
     return 0;
-}
-
-void tamd_dgram_set_timing(void* h, int on) {
-    Framer* s = (Framer*)h;
-    if (!s) return;
-    std::lock_guard<std::mutex> lk(s->mu);
-    hipSetDevice(s->device);
-    s->timing = on != 0;
-    for (hipEvent_t& e : s->ev)
-        if (on && !e && hipEventCreate(&e) != hipSuccess) e = nullptr;
-}
-
-void tamd_dgram_kernel_ms(void* h, double* out, unsigned n) {
-    Framer* s = (Framer*)h;
-    if (!s || !out) return;
-    std::lock_guard<std::mutex> lk(s->mu);
-    const double v[4] = {s->ms[kBuild], s->ms[kParse], (double)s->launches[kBuild], (double)s->launches[kParse]};
-    for (unsigned i = 0; i < n && i < 4; ++i) out[i] = v[i];
-    for (int k = 0; k < kKinds; ++k) { s->ms[k] = 0; s->launches[k] = 0; }
 }
 
 }  // extern "C"

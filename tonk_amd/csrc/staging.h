@@ -1,4 +1,6 @@
-// staging.h -- the pinned staging buffer of the batched interfaces (batch.cpp, seal.cpp).
+// staging.h -- the pinned staging buffer of the batched interfaces' handles (handle.h: batch.cpp,
+// seal.cpp, dgram.cpp).  It is freed with its handle (unlike lz_host.h's Buffer, which has static
+// lifetime and is never freed at exit).
 #pragma once
 #include <hip/hip_runtime.h>
 
