@@ -1,5 +1,6 @@
 # Test-only: the block reader of the decompression kernel (tonk_amd/csrc/unlz.h) as a serial host
-# walk against the reference's zstd (tests/test_decompress.py); the second target is the same
+# walk and on 64 emulated lanes against the reference's zstd (tests/test_decompress.py), with the
+# generator of the directed blocks; the second target is the same
 # program under the address and undefined-behaviour sanitizers (their runtimes linked in), run on
 # its own.
 #   make -C tests/native -f unlz.mk

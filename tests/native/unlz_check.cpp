@@ -1,6 +1,7 @@
-// unlz_check.cpp -- TEST ONLY.  A serial host walk of the block reader the decompression kernel
-// uses (tonk_amd/csrc/unlz.h alone, one "lane"), against the reference's zstd
-// (oracle/_ref/libmsgcodec_ref.so: MessageCompressor / MessageDecompressor restated).
+// unlz_check.cpp -- TEST ONLY.  The block reader the decompression kernel uses
+// (tonk_amd/csrc/unlz.h alone) on the host: as a serial walk (one "lane") and on 64 emulated
+// lanes, against the reference's zstd (oracle/_ref/libmsgcodec_ref.so: MessageCompressor /
+// MessageDecompressor restated).
 //
 //   unlz_check check <streams> [<rewrites out>]
 //       every message of every stream is compressed by the reference and restored by the walk
@@ -23,17 +24,45 @@
 //   unlz_check ring
 //       the compressor's form of the history-ring rule (lz.h RingTrack) and the decoder's
 //       (tamd_unlz_place) side by side: 10 maximum sizes x 200 seeded streams x 400 lengths.
+//   unlz_check directed <cases out>
+//       blocks written from chosen parses (lz_host.h lz_host_write), aimed at the boundaries of
+//       the reader's lane code: the chunk of 64 sequences, the waits for bytes just written, the
+//       lane count as a match's period and length, matches into and across the previous ring
+//       segment, block and literal sizes around 256 and 1536.  Every block goes through the walk
+//       and the reference decompressor; both must restore the message.  Prints one JSON record
+//       per group (the reader's path counters and facts); <cases out>: the corpus with verdicts.
+//   unlz_check lanes <streams> [blocks=<file>] [cases=<file>] [skip=<function>:<line>]
+//       the reader as the kernel runs it: 64 lanes as fibres, each calling unlz.h with
+//       (lane, 64) inside the kernel's message loop restated, TAMD_UNLZ_SYNC() = wait until every
+//       lane has arrived.  Between two syncs one lane at a time runs its phase to the end, in
+//       three orders (ascending, descending, a seeded shuffle redrawn at every sync).  Restored
+//       bytes, status, repeat offsets and ring bookkeeping after every message must equal the
+//       walk's (and the reference's bytes).  Inputs: the reference's blocks of <streams>, block
+//       files without verdicts (check's rewrites) and case files with them (directed).  skip=:
+//       all lanes run through that one sync site without waiting.
+//   unlz_check sens <streams> [blocks=<file>] [cases=<file>]
+//       for every sync site the lanes reach (over the block files, the case files and the first
+//       messages of every stream): does skipping it change any output under any order?
+//   unlz_check reach <streams> [blocks=<file>] [cases=<file>]
+//       the walk over the same kinds of input; prints how often each path and each outcome of a
+//       wait ran (which paths a set of inputs reaches, e.g. the device's).
 //
 // Stream files: "UNLZ", u32 streams; per stream u32 max, u32 messages; per message u32 is_block,
 // u32 bytes, the bytes.  Case files add per message i32 status, u32 restored, the restored bytes.
 static unsigned long long g_cnt[64];
 #define TAMD_UNLZ_COUNT(what) (++g_cnt[what])
+// (a sync knows where it stands; outside the lanes / sens modes it does nothing)
+static void emu_sync(const char* func, int line);
+#define TAMD_UNLZ_SYNC() emu_sync(__func__, __LINE__)
 #include "../../tonk_amd/csrc/unlz.h"
 #include "lz_host.h"
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <sys/wait.h>
+#include <ucontext.h>
+#include <unistd.h>
 
 #include <algorithm>
 #include <atomic>
@@ -62,7 +91,7 @@ struct Stream {
     std::vector<Msg> msgs;
 };
 
-static bool read_streams(const char* path, std::vector<Stream>* out) {
+static bool read_streams(const char* path, std::vector<Stream>* out, bool verdicts = false) {
     FILE* f = fopen(path, "rb");
     if (!f) return false;
     char magic[4];
@@ -79,6 +108,11 @@ static bool read_streams(const char* path, std::vector<Stream>* out) {
             g.is_block = isb != 0;
             g.data.resize(len);
             if (ok && len) ok = fread(g.data.data(), 1, len, f) == len;
+            if (ok && verdicts) {  // (a case file's verdicts are skipped: the walk gives them again)
+                int32_t status = 0;
+                uint32_t r = 0;
+                ok = fread(&status, 4, 1, f) == 1 && fread(&r, 4, 1, f) == 1 && r <= (1u << 20) && fseek(f, (long)r, SEEK_CUR) == 0;
+            }
             st.msgs.push_back(g);
         }
         out->push_back(st);
@@ -285,16 +319,40 @@ static const char* kCntName[TAMD_CNT_N] = {
 
 // Blocks through the walk and the reference side by side; `want`: the original messages (null:
 // only the two decoders are compared).
-static int run_pair(const std::vector<Msg>& blocks, const std::vector<Msg>* want, uint32_t max, size_t s, const char* what) {
+// (`seen`: the walk's bytes and stream state after every message, and what the reader says of the block)
+struct Seen {
+    Bytes bytes;
+    uint32_t rep[3], next, dict_len;
+    uint32_t nseq, lit_type, n_streams, lit_sel, nbig;
+    int32_t status;
+};
+// (`rejects`: the stream's last message is a block that the walk and the reference both reject)
+static int run_pair(const std::vector<Msg>& blocks, const std::vector<Msg>* want, uint32_t max, size_t s, const char* what,
+                    std::vector<Seen>* seen = nullptr, bool rejects = false) {
     Walk wk(max);
     RefDec rd(max);
     Bytes a, b;
     for (size_t k = 0; k < blocks.size(); ++k) {
         const int32_t rc = wk.feed(blocks[k], &a);
         const int r = rd.feed(blocks[k], &b);
-        if (rc || r <= 0) return fail(what, s, k, rc, r);
+        const bool last_rejected = rejects && k + 1 == blocks.size();
+        if (last_rejected ? (rc == 0 || r > 0) : (rc || r <= 0)) return fail(what, s, k, rc, r);
         if (a != b) return fail("walk differs from the reference decompressor", s, k);
-        if (want && a != (*want)[k].data) return fail("walk differs from the message", s, k);
+        if (want && !last_rejected && a != (*want)[k].data) return fail("walk differs from the message", s, k);
+        if (seen) {
+            Seen e;
+            e.bytes = a;
+            e.status = rc;
+            for (int i = 0; i < 3; ++i) e.rep[i] = wk.S->rep[i];
+            e.next = wk.S->next;
+            e.dict_len = wk.S->dict_len;
+            e.nseq = wk.W->nseq;
+            e.lit_type = wk.W->lit_type;
+            e.n_streams = wk.W->n_streams;
+            e.lit_sel = wk.W->lit_sel;
+            e.nbig = wk.W->nbig;
+            seen->push_back(e);
+        }
     }
     return 0;
 }
@@ -821,11 +879,772 @@ static int mode_ring() {
     return 0;
 }
 
+static const char* kWaitName[TAMD_CNT_ALL - TAMD_CNT_N] = {"ext_wait", "ext_no_wait", "cross_rest", "cross_none",
+                                                            "match_wait", "match_no_wait"};
+
+static void print_counters(const unsigned long long* c, const char* sep) {
+    for (int i = 0; i < TAMD_CNT_N; ++i) printf("%s\"%s\": %llu", i ? sep : "", kCntName[i], c[i]);
+}
+
+// ---- directed blocks -------------------------------------------------------------------------
+// The generator chooses the parse: literals are seeded bytes, every match is copied from the
+// history at its offset, and lz_host_write writes the block.  The history is kept as the decoder
+// holds it (the ring rule restated: write offset, previous segment), and beside it RingTrack says
+// where the compressor's window starts: a match that would start before it is a generator bug,
+// except where a case says `outside` (below: the one wait no in-window block can reach).
+struct Seq {
+    uint32_t ll, ml, off;
+};
+struct Gen {
+    uint32_t max, next = 0, dict_len = 0, rng;
+    RingTrack rt;
+    Bytes ring;
+    const uint8_t* fse;
+    std::vector<Msg> blocks;  // what the decoder is given
+    std::vector<Msg> want;    // the messages
+    std::string err;
+    Gen(uint32_t mx, uint32_t seed, const uint8_t* f) : max(mx), rng(seed * 2654435761u + 12345u), ring(TAMD_UNLZ_RING), fse(f) {
+        rt.max = mx;
+    }
+    // alphabet 0: skewed (symbol s with probability 2^-(s+1), s < 20); else uniform below it
+    uint8_t byte(uint32_t alphabet) {
+        rng = rng * 1664525u + 1013904223u;
+        const uint32_t v = rng >> 8;
+        if (alphabet) return (uint8_t)(v % alphabet);
+        uint32_t s = 0;
+        while (s < 19 && ((v >> s) & 1u)) ++s;
+        return (uint8_t)s;
+    }
+    uint64_t place(uint32_t n, uint64_t* win) {
+        if (next + max > TAMD_UNLZ_RING) {
+            if (next) dict_len = next;
+            next = 0;
+        }
+        uint64_t pos = 0;
+        rt.place(n, &pos, win);
+        return pos;
+    }
+    void plain(uint32_t n, uint32_t alphabet) {  // a message sent as it is: history
+        uint64_t win = 0;
+        place(n, &win);
+        Msg m;
+        for (uint32_t i = 0; i < n; ++i) m.data.push_back(ring[next + i] = byte(alphabet));
+        next += n;
+        blocks.push_back(m);
+        want.push_back(m);
+    }
+    bool block(const std::vector<Seq>& seqs, uint32_t tail, uint32_t alphabet, bool fitted, bool huffman = true,
+               bool outside = false) {
+        uint32_t n = tail;
+        for (const Seq& s : seqs) n += s.ll + s.ml;
+        if (n == 0 || n > max) return bad("message size");
+        uint64_t win = 0;
+        const uint64_t pos = place(n, &win);
+        LzHostStats st;
+        Msg m;
+        uint32_t q = next;
+        for (const Seq& s : seqs) {
+            for (uint32_t i = 0; i < s.ll; ++i) m.data.push_back(ring[q++] = byte(alphabet));
+            if (!outside && pos + (q - next) < win + s.off) return bad("match starts before the compressor's window");
+            if (s.ml < 3 || s.off == 0) return bad("match");
+            for (uint32_t i = 0; i < s.ml; ++i, ++q) {
+                uint32_t from;
+                if (s.off <= q) from = q - s.off;
+                else if (s.off - q <= dict_len) from = dict_len - (s.off - q);
+                else return bad("offset beyond the history");
+                m.data.push_back(ring[q] = ring[from]);
+            }
+            st.lo.push_back(s.ll | (s.ml << 16));
+            st.off.push_back(s.off);
+        }
+        for (uint32_t i = 0; i < tail; ++i) m.data.push_back(ring[q++] = byte(alphabet));
+        LzHostOptions opt;
+        opt.huffman = huffman;
+        opt.fitted = fitted;
+        opt.max = max;
+        opt.slack = 16;  // (a directed block may be a little longer than its message)
+        Bytes out;
+        const uint32_t w = lz_host_write(m.data.data(), n, fse, opt, &out, &st);
+        if (!w) return bad("the writer did not write the block");
+        Msg b;
+        b.is_block = true;
+        b.data.assign(out.begin(), out.begin() + w);
+        next += n;
+        blocks.push_back(b);
+        want.push_back(m);
+        return true;
+    }
+    bool bad(const char* what) {
+        err = what;
+        return false;
+    }
+    // plain messages up to the ring's restart: the next message starts a new segment
+    void fill() {
+        while (next + max <= TAMD_UNLZ_RING) plain(max, 256);
+    }
+};
+
+struct Group {
+    const char* name;
+    std::vector<Gen> streams;
+};
+
+static bool directed_groups(const uint8_t* fse, std::vector<Group>* out) {
+    uint32_t seed = 1;
+    bool ok = true;
+    {  // chunks: nseq around the multiples of TAMD_UNLZ_CHUNK, every sequence (ll 1, ml 4); the first
+        // match of a chunk reads what the last match of the chunk before wrote (offset = ml).
+        // (127 / 128: the 1- / 2-byte count.  The 3-byte count needs 32,512 sequences, more than a
+        // 24,000-byte history holds: not here.)
+        Group g{"chunks", {}};
+        const uint32_t ns[] = {1, 63, 64, 65, 127, 128, 129, 191, 192, 193};
+        for (int fitted = 0; fitted < 2; ++fitted)
+            for (uint32_t n : ns) {
+                Gen s(1300, seed++, fse);
+                s.plain(300, 256);
+                s.plain(300, 256);
+                std::vector<Seq> q;
+                for (uint32_t i = 0; i < n; ++i) q.push_back(Seq{1, 4, i && i % TAMD_UNLZ_CHUNK == 0 ? 4u : 40u + (i * 7u) % 200u});
+                ok = ok && s.block(q, 0, 256, fitted != 0);
+                g.streams.push_back(s);
+            }
+        out->push_back(g);
+    }
+    {  // hazards: within one chunk, where a match's source lies against the bytes not yet waited for
+        Group g{"hazards", {}};
+        Gen s(1300, seed++, fse);
+        s.plain(400, 256);
+        s.plain(400, 256);
+        const uint32_t lls[] = {0, 1, 63, 64, 65, 128};
+        int k = 0;
+        for (uint32_t ll : lls) {
+            std::vector<std::vector<Seq>> pats;
+            if (ll) {
+                pats.push_back({Seq{ll, 8, ll}});  // the source is the literals just written
+                pats.push_back({Seq{ll, 8, 1}});
+            }
+            pats.push_back({Seq{3, 10, 200}, Seq{ll, 5, ll + 5}});          // the previous match's output
+            pats.push_back({Seq{ll, 6, ll + 6}});                           // ends where the chunk's bytes begin
+            pats.push_back({Seq{1, 8, 1}, Seq{ll, 5, 8 + ll + 5}});         // ends where the bytes since the last wait begin
+            pats.push_back({Seq{1, 8, 1}, Seq{ll, 3, 8 + ll + 1}});         // starts one byte below that point
+            pats.push_back({Seq{1, 8, 1}, Seq{2, 9, 3}, Seq{ll, 4, ll + 2}});  // three sequences, the third into the second
+            pats.push_back({Seq{ll, 6, ll + 300}});                         // wholly in older bytes: no wait
+            pats.push_back({Seq{1, 8, 1}, Seq{ll, 6, 8 + ll + 300}});
+            for (const auto& p : pats) ok = ok && s.block(p, 2, 256, (k++ & 1) != 0);
+        }
+        // one byte below the chunk's first byte to one byte past it (period 2)
+        ok = ok && s.block({Seq{1, 4, 2}}, 2, 256, false);
+        g.streams.push_back(s);
+        // the same decisions for a match into the previous segment
+        Gen e(1300, seed++, fse);
+        e.fill();
+        // The wait of an external match is taken only when it reads ring bytes that the current
+        // segment has overwritten in this very chunk.  The reader and the reference both follow
+        // such an offset (they read the ring as it physically is), no compressor writes one: the
+        // one case here outside the window.  First message of the new segment: 100 literals, then
+        // 20 bytes from ring offset 50.
+        const uint32_t dl = e.next;
+        ok = ok && e.block({Seq{100, 20, 100 + (dl - 50)}}, 2, 256, false, true, true);
+        uint32_t q = e.next + 10;
+        ok = ok && e.block({Seq{10, 12, q + 500}}, 2, 256, false);       // inside the segment before: no wait, no rest
+        q = e.next + 5;
+        ok = ok && e.block({Seq{5, 6 + 10, q + 6}}, 2, 256, true);        // crosses into the new segment
+        g.streams.push_back(e);
+        out->push_back(g);
+    }
+    {  // overlap: the period below, at and above the lane count; the length around one and two passes
+        Group g{"overlap", {}};
+        const uint32_t offs[] = {1, 2, 3, 7, 8, 9, 63, 64, 65}, mls[] = {3, 4, 63, 64, 65, 127, 128, 129, 300};
+        for (uint32_t off : offs) {
+            Gen s(1300, seed++, fse);
+            s.plain(300, 256);
+            s.plain(300, 256);
+            std::vector<Seq> q;
+            for (uint32_t ml : mls) q.push_back(Seq{2, ml, off});
+            ok = ok && s.block(q, 3, 256, (off & 1) != 0);
+            g.streams.push_back(s);
+        }
+        out->push_back(g);
+    }
+    {  // external: behind a ring restart, matches into the previous segment and across its end
+        Group g{"external", {}};
+        for (uint32_t max : {1300u, 4000u}) {
+            Gen s(max, seed++, fse);
+            s.fill();
+            for (int behind = 0; behind < 2; ++behind)
+                // kind 0: the continued part is longer than the offset; 1: inside; 2: up to the
+                // segment's last byte; 3..6: crossing by 1, 63, 64, 65 bytes
+                for (int kind = 0; kind < 7; ++kind) {
+                    const bool restart = s.next + max > TAMD_UNLZ_RING;
+                    const uint32_t at = restart ? 0u : s.next;
+                    std::vector<Seq> p;
+                    uint32_t q = at;
+                    if (behind) {
+                        p.push_back(Seq{3, 4, q + 3 + 200});
+                        q += 9;
+                    }
+                    const uint32_t ll = behind ? 2u : 0u;
+                    const uint32_t cross[] = {1, 63, 64, 65};
+                    if (kind == 0) p.push_back(Seq{ll, 9 + (q + 9 + 7), q + 9});
+                    else if (kind == 1) p.push_back(Seq{ll, 20, q + 300});
+                    else if (kind == 2) p.push_back(Seq{ll, 17, q + 17});
+                    else p.push_back(Seq{ll, 9 + cross[kind - 3], q + 9});
+                    ok = ok && s.block(p, 2, 256, (kind & 1) != 0);
+                }
+            g.streams.push_back(s);
+        }
+        out->push_back(g);
+    }
+    {  // sizes: block bytes around the copy's 256-byte pass and TAMD_LZ_MAX_MESSAGE; literal counts
+        // around the LDS buffer, the four streams' shares and the raw headers
+        Group g{"sizes", {}};
+        for (uint32_t target : {255u, 256u, 257u, 259u, 1535u, 1536u, 1537u}) {
+            uint32_t L = target - 8;
+            bool hit = false;
+            for (int it = 0; it < 8 && !hit; ++it) {
+                Gen s(4000, seed, fse);
+                s.plain(600, 256);
+                if (!s.block({Seq{L, 4, 100}}, 0, 256, false, false)) break;
+                const uint32_t b = (uint32_t)s.blocks.back().data.size();
+                if (b == target) {
+                    g.streams.push_back(s);
+                    hit = true;
+                } else {
+                    L += target - b;
+                }
+            }
+            ok = ok && hit;
+            ++seed;
+        }
+        const uint32_t hl[] = {256, 257, 258, 259, 1021, 1022, 1023, 1024, 1025, 1026, 1027, 1535, 1536, 1537};
+        int k = 0;
+        for (uint32_t L : hl) {
+            // (a uniform alphabet of 128: no symbol fills 64 table entries; it beats raw literals
+            // only where there are many)
+            const uint32_t alphabet = L > 1000 && (k++ & 1) ? 128u : 0u;
+            Gen s(4000, seed++, fse);
+            s.plain(600, alphabet);
+            ok = ok && s.block({Seq{L, 4, 100}}, 0, alphabet, true);
+            g.streams.push_back(s);
+        }
+        // the raw header's 1, 2 and 3 bytes (4095 literals do not fit a stream of 4000: 8000 there)
+        for (uint32_t L : {31u, 32u, 4095u, 4096u}) {
+            Gen s(L > 4000 ? 8000u : 4000u, seed++, fse);
+            s.plain(600, 256);
+            ok = ok && s.block({Seq{L, 4, 100}}, 0, 256, false, false);
+            g.streams.push_back(s);
+        }
+        out->push_back(g);
+    }
+    if (!ok)
+        for (const Group& g : *out)
+            for (size_t i = 0; i < g.streams.size(); ++i)
+                if (!g.streams[i].err.empty()) printf("FAIL directed %s stream %zu: %s\n", g.name, i, g.streams[i].err.c_str());
+    return ok;
+}
+
+static void print_set(const char* name, const std::vector<uint32_t>& v) {
+    std::vector<uint32_t> u(v);
+    std::sort(u.begin(), u.end());
+    u.erase(std::unique(u.begin(), u.end()), u.end());
+    printf(", \"%s\": [", name);
+    for (size_t i = 0; i < u.size(); ++i) printf("%s%u", i ? ", " : "", u[i]);
+    printf("]");
+}
+
+static int mode_directed(const char* cases_out) {
+    uint8_t fse[TAMD_FSE_BYTES];
+    tamd_fse_blob(fse);
+    std::vector<Group> groups;
+    if (!directed_groups(fse, &groups)) {
+        printf("FAIL the generator could not make a case\n");
+        return 1;
+    }
+    FILE* fo = cases_out ? fopen(cases_out, "wb") : nullptr;
+    if (cases_out && !fo) return fail("cannot write the cases", 0, 0);
+    uint32_t n_streams = 0;
+    for (const Group& g : groups) n_streams += (uint32_t)g.streams.size();
+    if (fo) {
+        fwrite("UNLZ", 1, 4, fo);
+        fwrite(&n_streams, 4, 1, fo);
+    }
+    size_t si = 0;
+    for (const Group& g : groups) {
+        unsigned long long before[TAMD_CNT_ALL], c[TAMD_CNT_ALL];
+        memcpy(before, g_cnt, sizeof(before));
+        std::vector<uint32_t> nseq, chunks, lit_type, n_str, lit_sel, bytes, nbig;
+        unsigned long long n_blocks = 0;
+        for (const Gen& s : g.streams) {
+            std::vector<Seen> seen;
+            if (run_pair(s.blocks, &s.want, s.max, si++, g.name, &seen)) return 1;
+            std::vector<Case> cs(s.blocks.size());
+            for (size_t k = 0; k < s.blocks.size(); ++k) {
+                cs[k].msg = s.blocks[k];
+                cs[k].restored = s.want[k].data;
+                if (!s.blocks[k].is_block) continue;
+                ++n_blocks;
+                const Seen& e = seen[k];
+                nseq.push_back(e.nseq);
+                chunks.push_back((e.nseq + TAMD_UNLZ_CHUNK - 1u) / TAMD_UNLZ_CHUNK);
+                lit_type.push_back(e.lit_type);
+                bytes.push_back((uint32_t)s.blocks[k].data.size());
+                if (e.lit_type >= 2) {
+                    n_str.push_back(e.n_streams);
+                    lit_sel.push_back(e.lit_sel);
+                }
+                if (e.lit_type == 2) nbig.push_back(e.nbig ? 1u : 0u);
+            }
+            if (fo) write_cases(fo, s.max, cs, true);
+        }
+        for (int i = 0; i < TAMD_CNT_ALL; ++i) c[i] = g_cnt[i] - before[i];
+        printf("{\"group\": \"%s\", \"streams\": %zu, \"blocks\": %llu", g.name, g.streams.size(), n_blocks);
+        print_set("nseq", nseq);
+        print_set("chunks", chunks);
+        print_set("lit_type", lit_type);
+        print_set("huf_streams", n_str);
+        print_set("lit_sel", lit_sel);
+        print_set("huf_big_symbol", nbig);
+        print_set("block_bytes", bytes);
+        printf(", \"paths\": {");
+        print_counters(c, ", ");
+        printf("}, \"waits\": {");
+        for (int i = TAMD_CNT_N; i < TAMD_CNT_ALL; ++i) printf("%s\"%s\": %llu", i > TAMD_CNT_N ? ", " : "", kWaitName[i - TAMD_CNT_N], c[i]);
+        printf("}}\n");
+    }
+    if (fo) fclose(fo);
+    printf("ok\n");
+    return 0;
+}
+
+// ---- which paths a set of inputs reaches -------------------------------------------------------
+struct Input {
+    uint32_t max;
+    std::vector<Msg> blocks;
+    std::vector<Msg> want;  // the messages, where they are known (else empty)
+    std::string from;
+    bool rejects = false;   // the last message is a block to be rejected (sens only)
+};
+
+// The reference's blocks of a stream file (`limit` > 0: the first `limit` messages of each), then
+// the streams of block files (blocks=) and case files (cases=) as they are.
+static bool collect_inputs(int argc, char** argv, size_t limit, std::vector<Input>* out) {
+    std::vector<Stream> streams;
+    if (!read_streams(argv[2], &streams) || streams.empty()) return false;
+    for (const Stream& st : streams) {
+        Input in;
+        in.max = st.max;
+        in.blocks = ref_blocks(st);
+        in.want = st.msgs;
+        if (limit && in.blocks.size() > limit) {
+            in.blocks.resize(limit);
+            in.want.resize(limit);
+        }
+        in.from = argv[2];
+        out->push_back(in);
+    }
+    for (int i = 3; i < argc; ++i) {
+        const std::string a = argv[i];
+        const bool cases = a.compare(0, 6, "cases=") == 0;
+        if (!cases && a.compare(0, 7, "blocks=") != 0) continue;
+        std::vector<Stream> more;
+        const char* path = argv[i] + (cases ? 6 : 7);
+        if (!read_streams(path, &more, cases)) return false;
+        for (const Stream& st : more) {
+            Input in;
+            in.max = st.max;
+            in.blocks = st.msgs;
+            in.from = path;
+            out->push_back(in);
+        }
+    }
+    return true;
+}
+
+static int mode_reach(int argc, char** argv) {
+    std::vector<Input> inputs;
+    if (!collect_inputs(argc, argv, 0, &inputs)) return fail("cannot read the inputs", 0, 0);
+    for (size_t s = 0; s < inputs.size(); ++s)
+        if (run_pair(inputs[s].blocks, inputs[s].want.empty() ? nullptr : &inputs[s].want, inputs[s].max, s, "block rejected")) return 1;
+    for (int i = 0; i < TAMD_CNT_N; ++i) printf("path %s %llu\n", kCntName[i], g_cnt[i]);
+    for (int i = TAMD_CNT_N; i < TAMD_CNT_ALL; ++i) printf("wait %s %llu\n", kWaitName[i - TAMD_CNT_N], g_cnt[i]);
+    printf("ok\n");
+    return 0;
+}
+
+// ---- the reader on 64 emulated lanes -----------------------------------------------------------
+// Every lane is a fibre that runs the kernel's message loop (unlz.hip, restated in emu_lane) and
+// calls unlz.h with (lane, 64).  A sync hands control back to the scheduler; when every lane has
+// arrived the scheduler starts the next phase, one lane after the other in the order of the run.
+// Any order of the lanes between two syncs is a legal execution of a wave, so a phase that reads
+// what another lane of the same phase writes gives wrong bytes here, every time.
+//
+// A sync in code that only one lane runs (lane 0 builds the Huffman weights' table by itself with
+// nl = 1) holds nobody up on the device, where the other lanes wait at the branch's end: a lane
+// found at another site than the rest is run on alone until it joins them.
+struct Site {
+    const char* func;
+    int line;
+};
+static bool same_site(const Site& a, const Site& b) { return a.line == b.line && strcmp(a.func, b.func) == 0; }
+
+struct Emu {
+    static const uint32_t NL = 64, STACK = 256u << 10;
+    ucontext_t sched, lane[NL];
+    char* stacks = nullptr;
+    bool active = false, done[NL];
+    Site at[NL];
+    uint32_t cur = 0, rng = 1;
+    Site skip = {"", -1};
+    std::vector<Site> reached;
+    void (*body)(uint32_t) = nullptr;
+};
+static Emu g_emu;
+
+static void emu_sync(const char* func, int line) {
+    Emu& E = g_emu;
+    if (!E.active) return;
+    if (line == E.skip.line && strcmp(func, E.skip.func) == 0) return;
+    E.at[E.cur].func = func;
+    E.at[E.cur].line = line;
+    swapcontext(&E.lane[E.cur], &E.sched);
+}
+
+static void emu_entry(unsigned lane) {
+    g_emu.body(lane);
+    g_emu.done[lane] = true;
+}
+
+// Runs `body` on 64 lanes; order 0: ascending, 1: descending, 2: a shuffle redrawn at every sync.
+// False when the lanes did not stay together (possible only with a site skipped).
+static bool emu_run(void (*body)(uint32_t), int order, uint32_t seed) {
+    Emu& E = g_emu;
+    if (!E.stacks) E.stacks = (char*)malloc((size_t)Emu::NL * Emu::STACK);
+    E.body = body;
+    E.rng = seed * 2654435761u + 1u;
+    for (uint32_t l = 0; l < Emu::NL; ++l) {
+        getcontext(&E.lane[l]);
+        E.lane[l].uc_stack.ss_sp = E.stacks + (size_t)l * Emu::STACK;
+        E.lane[l].uc_stack.ss_size = Emu::STACK;
+        E.lane[l].uc_link = &E.sched;
+        makecontext(&E.lane[l], (void (*)())emu_entry, 1, (unsigned)l);
+        E.done[l] = false;
+    }
+    E.active = true;
+    bool together = true;
+    uint32_t perm[Emu::NL];
+    for (;;) {
+        for (uint32_t l = 0; l < Emu::NL; ++l) perm[l] = order == 1 ? Emu::NL - 1u - l : l;
+        if (order == 2)
+            for (uint32_t l = Emu::NL - 1u; l > 0; --l) {
+                E.rng = E.rng * 1664525u + 1013904223u;
+                std::swap(perm[l], perm[(E.rng >> 8) % (l + 1u)]);
+            }
+        for (uint32_t i = 0; i < Emu::NL; ++i) {
+            E.cur = perm[i];
+            swapcontext(&E.sched, &E.lane[E.cur]);
+        }
+        // where the most lanes stand is where the wave stands
+        uint32_t best = 0, best_n = 0, n_done = 0;
+        for (uint32_t l = 0; l < Emu::NL; ++l) {
+            if (E.done[l]) {
+                ++n_done;
+                continue;
+            }
+            uint32_t n = 0;
+            for (uint32_t m = 0; m < Emu::NL; ++m) n += !E.done[m] && same_site(E.at[l], E.at[m]);
+            if (n > best_n) {
+                best_n = n;
+                best = l;
+            }
+        }
+        if (n_done == Emu::NL) break;
+        if (n_done || best_n <= Emu::NL / 2u) {
+            together = false;
+            break;
+        }
+        const Site here = E.at[best];
+        for (uint32_t i = 0; i < Emu::NL && together; ++i) {
+            E.cur = perm[i];
+            for (uint32_t tries = 0; !same_site(E.at[E.cur], here); ++tries) {
+                if (tries > 100000u) together = false;
+                else swapcontext(&E.sched, &E.lane[E.cur]);
+                if (E.done[E.cur]) together = false;
+                if (!together) break;
+            }
+        }
+        if (!together) break;
+        bool known = false;
+        for (const Site& s : E.reached) known = known || same_site(s, here);
+        if (!known) E.reached.push_back(here);
+    }
+    E.active = false;
+    return together;
+}
+
+// One stream as the kernel's job sees it.  `pad`: bytes behind every buffer (a run with a site
+// skipped may decode nonsense; most of it then shows as wrong bytes and not as a fault).
+struct EmuJob {
+    uint32_t cap = 0;
+    const std::vector<Msg>* msgs = nullptr;
+    tamd_unlz_state* S = nullptr;
+    tamd_unlz_work* W = nullptr;
+    uint8_t *ring = nullptr, *lit = nullptr, *big = nullptr, *blk = nullptr, *in = nullptr, *out = nullptr;
+    std::vector<size_t> in_at;
+    std::vector<int32_t> status;
+    std::vector<uint32_t> restored;
+    std::vector<Seen> state;
+};
+static EmuJob g_job;
+
+// unlz.hip's loop over a job's messages (a fresh stream; every message has an output slot).
+static void emu_lane(uint32_t lane) {
+    EmuJob& J = g_job;
+    tamd_unlz_state* S = J.S;
+    if (lane == 0) tamd_unlz_reset(S);
+    emu_sync("message_loop", 1);
+    for (size_t mi = 0; mi < J.msgs->size(); ++mi) {
+        const Msg& m = (*J.msgs)[mi];
+        const uint32_t n = (uint32_t)m.data.size();
+        int32_t rc = S->failed ? TAMD_UNLZ_E_FAILED : (n == 0 || n > J.cap) ? TAMD_UNLZ_E_SIZE : TAMD_UNLZ_OK;
+        uint32_t r = 0;
+        if (!rc) {
+            uint8_t* const o = J.out + mi * (size_t)J.cap;
+            const uint8_t* src = J.in + J.in_at[mi];
+            if (lane == 0) tamd_unlz_place(S, J.cap);
+            if (m.is_block) {
+                if (n <= TAMD_LZ_MAX_MESSAGE) {
+                    for (uint32_t i = 4u * lane; i < n; i += 256u) memcpy(J.blk + i, src + i, 4);
+                    src = J.blk;
+                }
+                emu_sync("message_loop", 2);
+                rc = tamd_unlz_block(S, J.W, J.ring, src, n, J.cap, o, J.lit, TAMD_LZ_MAX_MESSAGE, J.big, J.cap, lane, Emu::NL, &r);
+            } else {
+                emu_sync("message_loop", 3);
+                tamd_unlz_insert(S, J.ring, src, n, o, lane, Emu::NL);
+                r = n;
+            }
+        }
+        if (lane == 0) {
+            J.status[mi] = rc;
+            J.restored[mi] = rc ? 0u : r;
+            if (rc && !S->failed) S->failed = rc;
+            for (int i = 0; i < 3; ++i) J.state[mi].rep[i] = S->rep[i];
+            J.state[mi].next = S->next;
+            J.state[mi].dict_len = S->dict_len;
+        }
+        emu_sync("message_loop", 4);
+    }
+}
+
+// One input on the lanes in one order against what the walk saw; null when all is equal.
+static const char* emu_input(const Input& in, const std::vector<Seen>& want, int order, uint32_t seed, size_t pad, size_t* where) {
+    EmuJob& J = g_job;
+    const size_t n_msgs = in.blocks.size();
+    J.cap = in.max;
+    J.msgs = &in.blocks;
+    J.in_at.assign(n_msgs, 0);
+    size_t in_bytes = 0;
+    for (size_t k = 0; k < n_msgs; ++k) {
+        J.in_at[k] = in_bytes;
+        in_bytes += in.blocks[k].data.size() + 32;  // (the device's input has 32 readable bytes behind it)
+    }
+    const size_t out_bytes = n_msgs * (size_t)in.max;
+    // (LDS is not cleared on the device: the state and the working memory start as garbage)
+    J.S = (tamd_unlz_state*)malloc(sizeof(tamd_unlz_state));
+    J.W = (tamd_unlz_work*)malloc(sizeof(tamd_unlz_work));
+    memset(J.S, 0xEE, sizeof(tamd_unlz_state));
+    // (with a site skipped the working memory starts as zeros: a lane that ran ahead on garbage
+    // counts would not come to an end, and what it read of the block before shows the same)
+    memset(J.W, pad > 64 ? 0 : 0xEE, sizeof(tamd_unlz_work));
+    J.ring = (uint8_t*)calloc(1, TAMD_UNLZ_RING + pad);
+    J.lit = (uint8_t*)calloc(1, TAMD_LZ_MAX_MESSAGE + pad);
+    J.big = (uint8_t*)calloc(1, in.max + pad);
+    J.blk = (uint8_t*)calloc(1, TAMD_LZ_MAX_MESSAGE + 16 + pad);
+    J.in = (uint8_t*)calloc(1, in_bytes + pad);
+    J.out = (uint8_t*)malloc(out_bytes + pad);
+    memset(J.out, 0xA5, out_bytes + pad);
+    for (size_t k = 0; k < n_msgs; ++k) memcpy(J.in + J.in_at[k], in.blocks[k].data.data(), in.blocks[k].data.size());
+    J.status.assign(n_msgs, 1);
+    J.restored.assign(n_msgs, 0);
+    J.state.assign(n_msgs, Seen());
+    const char* diff = nullptr;
+    *where = 0;
+    if (!emu_run(emu_lane, order, seed)) diff = "the lanes did not stay together";
+    for (size_t k = 0; k < n_msgs && !diff; ++k) {
+        const uint8_t* o = J.out + k * (size_t)in.max;
+        const Seen& w = want[k];
+        *where = k;
+        if (J.status[k] != w.status) diff = "status";
+        else if (J.restored[k] != w.bytes.size()) diff = "restored length";
+        else if (memcmp(o, w.bytes.data(), w.bytes.size())) diff = "restored bytes";
+        else if (memcmp(J.state[k].rep, w.rep, sizeof(w.rep))) diff = "repeat offsets";
+        else if (J.state[k].next != w.next || J.state[k].dict_len != w.dict_len) diff = "ring offset or dictionary length";
+        else
+            for (size_t i = w.bytes.size(); i < in.max && !diff; ++i)
+                if (o[i] != 0xA5) diff = "a byte written behind the message";
+    }
+    free(J.S);
+    free(J.W);
+    free(J.ring);
+    free(J.lit);
+    free(J.big);
+    free(J.blk);
+    free(J.in);
+    free(J.out);
+    return diff;
+}
+
+// The walk and the reference over every input: what the lanes must reproduce.
+static int lanes_expect(const std::vector<Input>& inputs, std::vector<std::vector<Seen>>* want) {
+    want->resize(inputs.size());
+    for (size_t s = 0; s < inputs.size(); ++s)
+        if (run_pair(inputs[s].blocks, inputs[s].want.empty() ? nullptr : &inputs[s].want, inputs[s].max, s, "block rejected", &(*want)[s],
+                     inputs[s].rejects))
+            return 1;
+    return 0;
+}
+
+static const char* kOrderName[3] = {"ascending", "descending", "shuffled"};
+
+// Every input in one order; 0 when all equal.
+static int lanes_order(const std::vector<Input>& inputs, const std::vector<std::vector<Seen>>& want, int order, size_t pad) {
+    for (size_t s = 0; s < inputs.size(); ++s) {
+        size_t k = 0;
+        const char* diff = emu_input(inputs[s], want[s], order, (uint32_t)s, pad, &k);
+        if (diff) {
+            printf("DIFF %s order: input %zu (%s, max %u), message %zu: %s\n", kOrderName[order], s, inputs[s].from.c_str(), inputs[s].max, k, diff);
+            fflush(stdout);
+            return 1;
+        }
+    }
+    return 0;
+}
+
+static bool parse_site(const char* arg, std::string* func, Site* site) {
+    const char* colon = strchr(arg, ':');
+    if (!colon) return false;
+    func->assign(arg, colon);
+    site->func = func->c_str();
+    site->line = atoi(colon + 1);
+    return true;
+}
+
+static int mode_lanes(int argc, char** argv) {
+    std::vector<Input> inputs;
+    if (!collect_inputs(argc, argv, 0, &inputs)) return fail("cannot read the inputs", 0, 0);
+    std::string func;
+    bool skipping = false;
+    for (int i = 3; i < argc; ++i)
+        if (strncmp(argv[i], "skip=", 5) == 0) skipping = parse_site(argv[i] + 5, &func, &g_emu.skip);
+    std::vector<std::vector<Seen>> want;
+    if (lanes_expect(inputs, &want)) return 1;
+    size_t n_msgs = 0;
+    for (const Input& in : inputs) n_msgs += in.blocks.size();
+    fflush(stdout);
+    // the three orders side by side, a process each
+    pid_t pid[3];
+    for (int order = 0; order < 3; ++order) {
+        pid[order] = fork();
+        if (pid[order] == 0) _exit(lanes_order(inputs, want, order, skipping ? (4u << 20) : 64u));
+    }
+    int bad = 0;
+    for (int order = 0; order < 3; ++order) {
+        int st = 0;
+        waitpid(pid[order], &st, 0);
+        if (!WIFEXITED(st) || WEXITSTATUS(st) != 0) {
+            printf("FAIL %s order%s\n", kOrderName[order], WIFEXITED(st) ? "" : ": the run ended by a signal");
+            ++bad;
+        }
+    }
+    printf("lanes: %zu streams, %zu messages, 3 orders\n", inputs.size(), n_msgs);
+    if (bad) return 1;
+    printf("ok\n");
+    return 0;
+}
+
+static int mode_sens(int argc, char** argv) {
+    std::vector<Input> inputs;
+    if (!collect_inputs(argc, argv, 40, &inputs)) return fail("cannot read the inputs", 0, 0);
+    {
+        // The sync behind the Huffman streams carries the streams' verdicts to all lanes (the
+        // literals themselves are read behind later syncs), and a verdict differs from 0 only in
+        // a block that is rejected: the one such block of this mode.  A directed block with four
+        // Huffman streams gets a byte of its second stream changed until the walk finds the
+        // stream not consumed exactly (and the reference rejects the block as well).
+        uint8_t fse[TAMD_FSE_BYTES];
+        tamd_fse_blob(fse);
+        Gen s(4000, 77, fse);
+        s.plain(600, 0);
+        if (!s.block({Seq{1200, 4, 100}}, 0, 0, true)) return fail("sens: the Huffman block", 0, 0);
+        Input in;
+        in.max = s.max;
+        in.from = "a rejected Huffman stream";
+        in.rejects = true;
+        bool found = false;
+        const uint32_t third = (uint32_t)s.blocks.back().data.size() / 3u;
+        for (uint32_t at = third; at < third + 40u && !found; ++at) {
+            in.blocks = s.blocks;
+            in.blocks.back().data[at] ^= 0x5a;
+            Walk wk(s.max);
+            RefDec rd(s.max);
+            Bytes a;
+            wk.feed(in.blocks[0], &a);
+            rd.feed(in.blocks[0], &a);
+            found = wk.feed(in.blocks[1], &a) == TAMD_UNLZ_E_HUFSTREAM && wk.W->n_streams == 4 && rd.feed(in.blocks[1], &a) <= 0;
+        }
+        if (!found) return fail("sens: no rejected Huffman stream", 0, 0);
+        inputs.push_back(in);
+    }
+    // (the directed corpus and the rewrites first: they find most differences at once)
+    std::stable_sort(inputs.begin(), inputs.end(), [&](const Input& a, const Input& b) { return a.want.empty() && !b.want.empty(); });
+    std::vector<std::vector<Seen>> want;
+    if (lanes_expect(inputs, &want)) return 1;
+    // the sites reached: one run with nothing skipped (which must itself be clean)
+    if (lanes_order(inputs, want, 0, 64)) return 1;
+    const std::vector<Site> sites = g_emu.reached;
+    fflush(stdout);
+    const size_t jobs = 8;
+    std::vector<pid_t> pids(sites.size(), 0);
+    std::vector<int> verdict(sites.size(), -1);  // 0: no difference, 1: a difference, 2: ended by a signal
+    size_t started = 0, running = 0, finished = 0;
+    while (finished < sites.size()) {
+        while (started < sites.size() && running < jobs) {
+            const pid_t p = fork();
+            if (p == 0) {
+                g_emu.skip = sites[started];
+                alarm(100);
+                int differs = 0;
+                for (int order = 0; order < 3 && !differs; ++order) differs = lanes_order(inputs, want, order, 4u << 20);
+                _exit(differs);
+            }
+            pids[started++] = p;
+            ++running;
+        }
+        int st = 0;
+        const pid_t p = wait(&st);
+        for (size_t i = 0; i < started; ++i)
+            if (pids[i] == p) {
+                verdict[i] = WIFEXITED(st) ? WEXITSTATUS(st) : 2;
+                --running;
+                ++finished;
+            }
+    }
+    for (size_t i = 0; i < sites.size(); ++i)
+        printf("site %s %d %s\n", sites[i].func, sites[i].line,
+               verdict[i] == 0 ? "unneeded" : verdict[i] == 1 ? "necessary" : "necessary (the run without it ended by a signal)");
+    printf("ok\n");
+    return 0;
+}
+
 int main(int argc, char** argv) {
+    if (argc >= 2 && std::string(argv[1]) == "directed") return mode_directed(argc > 2 ? argv[2] : nullptr);
+    if (argc >= 3 && std::string(argv[1]) == "lanes") return mode_lanes(argc, argv);
+    if (argc >= 3 && std::string(argv[1]) == "sens") return mode_sens(argc, argv);
+    if (argc >= 3 && std::string(argv[1]) == "reach") return mode_reach(argc, argv);
     if (argc >= 2 && std::string(argv[1]) == "tables") return mode_tables();
     if (argc >= 2 && std::string(argv[1]) == "ring") return mode_ring();
     if (argc < 3) {
-        printf("usage: unlz_check tables | ring | check|mutants|bench <streams> ...\n");
+        printf("usage: unlz_check tables | ring | directed [<cases out>] | check|mutants|bench|lanes|sens|reach <streams> ...\n");
         return 2;
     }
     std::vector<Stream> streams;

@@ -2,14 +2,26 @@
 (include/tonk_compress.h tamd_decompress*, tonk_amd/csrc/unlz.h / unlz.hip / decompress.cpp).
 
 Parity is the reference's own pair (oracle/_ref/libmsgcodec_ref.so): its compressor's blocks are
-the input, its decompressor's bytes the expected output.  The CPU tests run the block reader as a
-serial host walk (tests/native/unlz_check.cpp) over every format path, and over malformed blocks
-under the address and undefined-behaviour sanitizers; the GPU tests run the kernel through the
-per-message API, the batch and the device-resident chain.
+the input, its decompressor's bytes the expected output.  What is checked where
+(tests/native/unlz_check.cpp is the host program of all CPU tests):
+
+  one lane (the serial host walk)  every format path against the reference (check); malformed
+      blocks and the directed corpus under the address and undefined-behaviour sanitizers
+      (mutants, directed); the directed corpus reaches its targets; the ring rule; which paths
+      the device's inputs reach (reach).
+  64 emulated lanes  the lane protocol without a GPU: where the syncs stand, the rule that
+      decides when a match waits for bytes just written, the lane strides, the chunks of 64
+      sequences (lanes); every sync site shown necessary or listed with the reason why no valid
+      block can show it (sens); the decode-table build phase by phase (tables).
+  device  the kernel through the per-message API, the batch and the device-resident chain: the
+      reference's and the GPU compressor's blocks of gpu_streams(), the Repeat rewrites and
+      hand-made blocks, the directed corpus (batch with canaries, and per message), malformed
+      blocks with the walk's verdicts, concurrent callers, recycled device memory.
 """
 from __future__ import annotations
 
 import ctypes
+import json
 import os
 import subprocess
 
@@ -99,7 +111,7 @@ def test_ring_rule_of_compressor_and_decoder_agree():
     assert counts[1] > 0 and counts[2] > 0, counts
 
 
-def test_malformed_blocks_under_sanitizers(stream_file, mutant_cases, tmp_path):
+def test_malformed_blocks_under_sanitizers(stream_file, mutant_cases, directed_cases, tmp_path):
     """Truncations, bit flips, an offset too far, a capacity too small: no sanitizer report, every
     unmutated block accepted, and whatever the walk accepts the reference restores the same.  The
     sanitizer build is made and run here only (a CPU test); it chooses the same 64 cases with the
@@ -115,6 +127,174 @@ def test_malformed_blocks_under_sanitizers(stream_file, mutant_cases, tmp_path):
     assert plain.returncode == 0 and plain.stdout == r.stdout
     with open(out, "rb") as a, open(plain_out, "rb") as b:
         assert a.read() == b.read()
+    # the directed corpus once under the same build: generator, block writer and walk
+    plain, plain_out = directed_cases
+    out = str(tmp_path / "directed.bin")
+    r = subprocess.run([exe, "directed", out], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-2000:] + r.stderr[-4000:]
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
+    assert plain.stdout == r.stdout
+    with open(out, "rb") as a, open(plain_out, "rb") as b:
+        assert a.read() == b.read()
+
+
+@pytest.fixture(scope="module")
+def rewrites_file(stream_file, tmp_path_factory):
+    """The Repeat rewrites and the hand-made blocks of `check`, as blocks (no verdicts)."""
+    exe = unlz_check()
+    out = str(tmp_path_factory.mktemp("unlz") / "rewrites.bin")
+    r = subprocess.run([exe, "check", stream_file, out], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    return out
+
+
+@pytest.fixture(scope="module")
+def directed_cases(tmp_path_factory):
+    """The directed corpus (unlz_check directed): the run and its case file.  Generated from
+    seeds every time; the generator itself requires of every block that the walk and the
+    reference decompressor restore the message."""
+    exe = unlz_check()
+    out = str(tmp_path_factory.mktemp("unlz") / "directed.bin")
+    r = subprocess.run([exe, "directed", out], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-4000:] + r.stderr[-2000:]
+    return r, out
+
+
+WAITS = ("ext_wait", "ext_no_wait", "cross_rest", "cross_none", "match_wait", "match_no_wait")
+
+
+def test_directed_blocks_reach_their_targets(directed_cases):
+    """Each group of the directed corpus reached what it aims at, by the reader's own counters
+    and facts: chunks 1..4 chunks of sequences with every count around the multiples of 64;
+    hazards both outcomes of each of the three decisions to wait; external the matches into and
+    across the previous segment; overlap the overlapping match; sizes both literal buffers, one
+    and four Huffman streams, a symbol with and without a long table run, both sides of 1536
+    block bytes and the exact block sizes."""
+    r, path = directed_cases
+    rec = {x["group"]: x for x in map(json.loads, (ln for ln in r.stdout.splitlines() if ln.startswith("{")))}
+    assert set(rec) == {"chunks", "hazards", "overlap", "external", "sizes"}
+    assert rec["chunks"]["nseq"] == [1, 63, 64, 65, 127, 128, 129, 191, 192, 193]
+    assert rec["chunks"]["chunks"] == [1, 2, 3, 4]
+    for k in ("ll_predefined", "ml_predefined", "of_predefined"):  # predefined and fitted tables
+        assert 0 < rec["chunks"]["paths"][k] < rec["chunks"]["blocks"], k
+    assert all(rec["hazards"]["waits"][k] > 0 for k in WAITS), rec["hazards"]["waits"]
+    ext = rec["external"]
+    assert ext["paths"]["ext_dict_match"] > 0 and ext["paths"]["ext_dict_cross"] > 0 and ext["paths"]["ring_restart"] == 2
+    assert ext["waits"]["cross_rest"] > 0 and ext["waits"]["cross_none"] > 0
+    assert rec["overlap"]["paths"]["overlap_match"] >= 81
+    sz = rec["sizes"]
+    assert sz["lit_sel"] == [0, 1] and sz["huf_streams"] == [1, 4] and sz["huf_big_symbol"] == [0, 1] and sz["lit_type"] == [0, 2]
+    assert {255, 256, 257, 259, 1535, 1536, 1537} <= set(sz["block_bytes"])
+    assert min(sz["block_bytes"]) < 1536 < max(sz["block_bytes"])
+    cases = read_cases(path, True)
+    assert sum(x["streams"] for x in rec.values()) == len(cases)
+    assert 100 < sum(len(m) for _, m in cases) < 1000
+    assert all(st == 0 and len(want) <= mx for mx, msgs in cases for _, _, st, want in msgs)
+
+
+def test_reader_on_64_emulated_lanes(stream_file, rewrites_file, directed_cases):
+    """unlz_check lanes: the whole reader on 64 lanes run as fibres inside the kernel's message
+    loop, every sync a barrier, one lane at a time between two barriers, in ascending, descending
+    and shuffled order: bytes, status, repeat offsets, ring offset and dictionary length after
+    every message equal the one-lane walk's, over every stream of cpu_streams() as the reference
+    compresses it, the Repeat rewrites, the hand-made blocks and the directed corpus."""
+    exe = unlz_check()
+    r = subprocess.run([exe, "lanes", stream_file, "blocks=" + rewrites_file, "cases=" + directed_cases[1]],
+                       capture_output=True, text=True, timeout=120)
+    print(r.stdout[-2000:])
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-4000:] + r.stderr[-2000:]
+    assert ", 3 orders" in r.stdout
+
+
+def sync_ordinals():
+    """(function, line) -> the ordinal of that TAMD_UNLZ_SYNC() within its function of unlz.h."""
+    import re
+    out, func, n = {}, None, 0
+    with open(os.path.join(ROOT, "tonk_amd", "csrc", "unlz.h")) as f:
+        for no, ln in enumerate(f, 1):
+            m = re.match(r"TAMD_HD static inline .*?\b(tamd_\w+)\(", ln)
+            if m:
+                func, n = m.group(1), 0
+            if "TAMD_UNLZ_SYNC();" in ln and not ln.startswith("#"):
+                n += 1
+                out[(func, no)] = n
+    return out
+
+
+# Sync sites that must be shown necessary: skipping one changes an output under some lane order.
+NECESSARY_SYNCS = {
+    ("tamd_unlz_block", 2): "the chunk arrays are free: lane 0 may decode the next chunk into them",
+    ("tamd_unlz_block", 3): "the chunk is decoded: all lanes may execute it",
+    ("tamd_unlz_block", 4): "an external match reads ring bytes written since the last sync",
+    ("tamd_unlz_block", 5): "the rest of a crossing match reads its own first part",
+    ("tamd_unlz_block", 6): "a match reads bytes written since the last sync",
+    ("tamd_unlz_literals", 2): "the Huffman table is filled: the stream lanes may read it",
+    ("tamd_unlz_literals", 3): "the streams' verdicts are written: every lane returns the same one",
+    ("tamd_unlz_fse_table", 1): "cum / nxt / the low symbols' places are written: the spread may read them",
+    ("tamd_unlz_fse_table", 2): "the spread is complete: the states may be numbered",
+    ("tamd_unlz_fse_table", 3): "every lane has read nxt: the entries may move it on",
+    ("tamd_unlz_fse_table", 4): "nxt has moved on: the next group of states may read it",
+}
+# Sites that no valid block can show necessary, each with the reason.  Any other reached site
+# must be shown necessary as well (message_loop: the kernel's loop in unlz.hip, restated in
+# unlz_check.cpp; its syncs are numbered in the order of the kernel's source).
+UNNEEDED_SYNCS = {
+    ("tamd_unlz_block", 1): "lane 0's reset of the block's counters; their first readers stand behind tamd_unlz_seq_header's first sync too",
+    ("tamd_unlz_block", 7): "before lane 0 moves S->rep / S->next on: the other lanes hold q0 in a register and read neither before the loop's sync",
+    ("tamd_unlz_block", 8): "the message loop's sync follows at once",
+    ("tamd_unlz_seq_header", 3): "W->norm free again: tamd_unlz_fse_table's last sync already stands behind its last reader",
+    ("tamd_unlz_seq_header", 4): "S->have_pre is next read behind the sync of the next table's description",
+    ("tamd_unlz_seq_header", 5): "the chunk loop's first sync follows at once",
+    ("tamd_unlz_insert", 2): "the message loop's sync follows at once",
+    ("message_loop", 4): "guards S->failed and the status, which only a rejected block changes",
+}
+
+
+def test_sync_sites_are_each_necessary(stream_file, rewrites_file, directed_cases):
+    """unlz_check sens: for every sync site the lanes reach, the lanes run through that one site
+    without waiting (all alike), and the outputs are compared under the three orders.  Every site
+    of NECESSARY_SYNCS is reached and changes an output when skipped, so the emulation would see
+    it missing; every other reached site does as well or is listed in UNNEEDED_SYNCS."""
+    exe = unlz_check()
+    r = subprocess.run([exe, "sens", stream_file, "blocks=" + rewrites_file, "cases=" + directed_cases[1]],
+                       capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-4000:] + r.stderr[-2000:]
+    ordinal = sync_ordinals()
+    verdict = {}
+    for ln in r.stdout.splitlines():
+        if ln.startswith("site "):
+            _, func, line, what = ln.split(None, 3)
+            key = (func, int(line)) if func == "message_loop" else (func, ordinal[(func, int(line))])
+            verdict[key] = what
+            print(key, what)
+    for key in NECESSARY_SYNCS:
+        assert verdict.get(key, "not reached").startswith("necessary"), (key, verdict.get(key))
+    for key, what in verdict.items():
+        assert what.startswith("necessary") or key in UNNEEDED_SYNCS, (key, what)
+    for key in UNNEEDED_SYNCS:  # (the list holds nothing that has become necessary or is gone)
+        assert verdict.get(key) == "unneeded", (key, verdict.get(key))
+
+
+def test_gpu_inputs_reach_every_reader_path(rewrites_file, directed_cases, tmp_path):
+    """What the device is given reaches what the walk's streams reach: the one-lane walk with
+    counters over exactly gpu_streams() as the reference compresses them, the directed corpus and
+    the block file of test_gpu_repeat_rewrites_and_hand_made_blocks (the only source of the
+    Repeat modes, RLE literals and the repeat codes no level-1 compressor writes) runs all 32
+    paths and both outcomes of every wait."""
+    exe = unlz_check()
+    path = str(tmp_path / "gpu_streams.bin")
+    write_streams(path, gpu_streams())
+    def reach(*more):
+        r = subprocess.run([exe, "reach", path, "cases=" + directed_cases[1], *more], capture_output=True, text=True,
+                           timeout=120)
+        assert r.returncode == 0 and r.stdout.rstrip().endswith("ok"), r.stdout[-4000:] + r.stderr[-2000:]
+        counts = {ln.split()[1]: int(ln.split()[2]) for ln in r.stdout.splitlines() if ln.startswith(("path ", "wait "))}
+        assert len(counts) == 32 + len(WAITS)
+        return {k for k, v in counts.items() if v == 0}
+
+    # (the block file holds prefixes of cpu_streams() too: it is asked only for what nothing else has)
+    assert reach() <= {"lit_rle", "ll_repeat", "ml_repeat", "of_repeat", "rep1", "rep2", "rep_ll0_2", "rep_ll0_minus1"}
+    assert reach("blocks=" + rewrites_file) == set()
 
 
 def test_decompress_abi_exports_and_no_cpu_fallback():
@@ -135,12 +315,16 @@ def test_decompress_abi_exports_and_no_cpu_fallback():
 # --------------------------------------------------------------------------------------- GPU
 
 def gpu_streams():
+    """(test_gpu_inputs_reach_every_reader_path: with the directed corpus and the rewrites these
+    reach every path of the reader; the last two are there for the repeat offsets and for
+    Huffman literals in the job's scratch)"""
     return [(1300, tonk_unit_messages()), (1300, mixed_messages(300, 5)), (1300, skewed(120, 9, 1300))] + \
-           [(m, edge_case_messages(m)) for m in (1300, 4000, 24000)]
+           [(m, edge_case_messages(m)) for m in (1300, 4000, 24000)] + \
+           [(1300, rep_offsets(60, 3)), (8000, skewed(40, 9, 8000))]
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("which", range(6))
+@pytest.mark.parametrize("which", range(8))
 def test_gpu_decompressor_reference_blocks(which):
     """The per-message API on the reference compressor's blocks: the output equals the message
     every time (uncompressed messages go through insert_uncompressed)."""
@@ -161,7 +345,7 @@ def test_gpu_decompressor_reference_blocks(which):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("which", range(6))
+@pytest.mark.parametrize("which", range(8))
 def test_gpu_decompressor_gpu_blocks(which):
     """MessageCompressor's blocks restored by MessageDecompressor; the reference decompressor
     beside it as the tie-breaker."""
@@ -440,6 +624,67 @@ def test_gpu_rejects_malformed_blocks_like_the_host_walk(mutant_cases):
                     assert (body[i] == 0xA5).all(), (s, k)  # a later message of a failed stream
         assert any(st == STATUS_FAILED for st in status) and any(st not in (0, STATUS_FAILED) for st in status)
     hip.close()
+
+
+@pytest.mark.gpu
+def test_gpu_directed_blocks_batch(directed_cases):
+    """The directed corpus through decompress_batch on device memory, one call per maximum size,
+    the output slots between 64-byte canaries and filled with the canary byte: every status is 0,
+    every restored length and byte is the case file's, and nothing is written behind a message's
+    last byte."""
+    from tonk_amd.compress import decompress_batch
+    hip = Hip()
+    cases = read_cases(directed_cases[1], True)
+    n_blocks = 0
+    for max_bytes in sorted({c[0] for c in cases}):
+        group = [c[1] for c in cases if c[0] == max_bytes]
+        n_msgs = max(len(g) for g in group)
+        pad = (False, b"p" * 16, 0, b"p" * 16)  # (uncompressed, behind everything the generator made)
+        group = [g + [pad] * (n_msgs - len(g)) for g in group]
+        n_streams, total = len(group), len(group) * n_msgs
+        slots = np.zeros((total, max_bytes), dtype=np.uint8)
+        in_bytes, is_block = [], []
+        for s, g in enumerate(group):
+            for k, (isb, data, _, _) in enumerate(g):
+                slots[s * n_msgs + k, :len(data)] = np.frombuffer(data, dtype=np.uint8)
+                in_bytes.append(len(data))
+                is_block.append(int(isb))
+        n_blocks += sum(is_block)
+        d_in = hip.malloc(total * max_bytes + 32)
+        hip.upload(d_in, slots.reshape(-1))
+        d_out = hip.malloc(64 + total * max_bytes + 64, fill=0xA5)
+        restored, status, _ = decompress_batch(d_in, n_streams, n_msgs, in_bytes, is_block, max_bytes, d_out + 64)
+        out = hip.download(d_out, 64 + total * max_bytes + 64)
+        assert (out[:64] == 0xA5).all() and (out[-64:] == 0xA5).all()
+        body = out[64:-64].reshape(total, max_bytes)
+        for s, g in enumerate(group):
+            for k, (_, _, _, want) in enumerate(g):
+                i = s * n_msgs + k
+                assert status[i] == 0 and restored[i] == len(want), (max_bytes, s, k, status[i], restored[i])
+                assert body[i, :len(want)].tobytes() == want, (max_bytes, s, k)
+                assert (body[i, len(want):] == 0xA5).all(), (max_bytes, s, k)
+    hip.close()
+    assert n_blocks > 100
+
+
+@pytest.mark.gpu
+def test_gpu_directed_blocks_per_message(directed_cases):
+    """The same streams through MessageDecompressor.decompress / insert_uncompressed: the state
+    leaves and re-enters LDS at every message, and large literal sections go to the handle's own
+    scratch."""
+    from tonk_amd.compress import MessageDecompressor
+    cases = read_cases(directed_cases[1], True)
+    n_blocks = 0
+    for s, (max_bytes, msgs) in enumerate(cases):
+        dec = MessageDecompressor(max_bytes)
+        for k, (isb, data, _, want) in enumerate(msgs):
+            if isb:
+                assert dec.decompress(data) == want, (s, k)
+                n_blocks += 1
+            else:
+                dec.insert_uncompressed(data)
+        dec.close()
+    assert n_blocks > 100
 
 
 @pytest.mark.gpu

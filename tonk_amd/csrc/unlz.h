@@ -8,7 +8,8 @@
 // the same arguments: the serial parts run on lane 0 (or one lane per Huffman stream), the copies
 // and table fills are strided over the lanes, and TAMD_UNLZ_SYNC() separates a phase that writes
 // shared memory from one that reads it.  The kernel runs them with a wave (nl = 64); on the host
-// nl = 1 and TAMD_UNLZ_SYNC() is empty.  No libc.
+// nl = 1 and TAMD_UNLZ_SYNC() is empty (the tests also run 64 lanes as fibres, the sync a
+// barrier: unlz_check lanes).  No libc.
 //
 // Every read of the block, the literal buffer and the ring and every write of the ring and the
 // output is bounded; a block that would step outside is rejected with a negative status.
@@ -30,7 +31,11 @@ enum {
     TAMD_CNT_OF_PREDEF, TAMD_CNT_OF_RLE, TAMD_CNT_OF_FSE, TAMD_CNT_OF_REPEAT,
     TAMD_CNT_OFF_NEW, TAMD_CNT_REP0, TAMD_CNT_REP1, TAMD_CNT_REP2, TAMD_CNT_REP_LL0_1, TAMD_CNT_REP_LL0_2,
     TAMD_CNT_REP_LL0_DEC, TAMD_CNT_EXT_MATCH, TAMD_CNT_EXT_CROSS, TAMD_CNT_OVERLAP, TAMD_CNT_RESTART,
-    TAMD_CNT_N
+    TAMD_CNT_N,
+    // (behind the paths: the outcomes of tamd_unlz_block's decisions to wait for bytes just written)
+    TAMD_CNT_WAIT_EXT = TAMD_CNT_N, TAMD_CNT_NOWAIT_EXT, TAMD_CNT_CROSS_REST, TAMD_CNT_CROSS_NONE,
+    TAMD_CNT_WAIT_MATCH, TAMD_CNT_NOWAIT_MATCH,
+    TAMD_CNT_ALL
 };
 
 #define TAMD_UNLZ_RING TAMD_LZ_DICT  // kCompressionDictBytes (lz.h)
@@ -951,19 +956,28 @@ TAMD_HD static inline int32_t tamd_unlz_block(tamd_unlz_state* S, tamd_unlz_work
             tamd_unlz_resolve(q, off, ml, S->dict_len, &src, &len1);  // (checked by tamd_unlz_seq_chunk)
             if (len1) {  // external dictionary, then (maybe) on from the segment's start
                 if (src + len1 > dirty && src < q) {
+                    TAMD_UNLZ_COUNT(TAMD_CNT_WAIT_EXT);
                     TAMD_UNLZ_SYNC();
                     dirty = q;
+                } else {
+                    TAMD_UNLZ_COUNT(TAMD_CNT_NOWAIT_EXT);
                 }
                 tamd_unlz_put_match(ring, q, src, len1, 0, out, p, lane, nl);
                 if (ml > len1) {
+                    TAMD_UNLZ_COUNT(TAMD_CNT_CROSS_REST);
                     TAMD_UNLZ_SYNC();  // (the rest may read what was just written: distance = off)
                     dirty = q + len1;
                     tamd_unlz_put_match(ring, q + len1, 0, ml - len1, off, out, p + len1, lane, nl);
+                } else {
+                    TAMD_UNLZ_COUNT(TAMD_CNT_CROSS_NONE);
                 }
             } else {
                 if (q > dirty && src + (ml < off ? ml : off) > dirty) {
+                    TAMD_UNLZ_COUNT(TAMD_CNT_WAIT_MATCH);
                     TAMD_UNLZ_SYNC();
                     dirty = q;
+                } else {
+                    TAMD_UNLZ_COUNT(TAMD_CNT_NOWAIT_MATCH);
                 }
                 tamd_unlz_put_match(ring, q, src, ml, off < ml ? off : 0u, out, p, lane, nl);
             }
