@@ -34,8 +34,8 @@
     expansion back to whole numbers on the receiving side (Tonk's writeNonce, its sequence
     compression and Counter::ExpandFromTruncated); the check "Reliable data sent with no sequence
     number", which is a test of the flags byte against reliable_bytes; anti-replay; the delivery
-    of the parsed messages; decompression of Compressed bodies (tonk_compress.h restores them; the
-    parse returns where they are); handshake contents; Tonk's queueing of messages into datagrams;
+    of the parsed messages; decompression of Compressed bodies (tonk_compress_batch.h restores them
+    where the parse found them); handshake contents; Tonk's queueing of messages into datagrams;
     asynchronous calls.  OnlyFEC datagrams are not parsed: the caller sees the flag in
     tamd_seal_footers' bytes and hands the message section to tamd_batch_decoder_add_recovery.
 */

@@ -15,16 +15,19 @@ import ctypes
 import os
 import subprocess
 
-__all__ = ["LIB_PATH", "build", "lib", "Session", "WorkloadParams", "loss_threshold", "ge_thresholds",
+__all__ = ["LIB_PATH", "CBATCH_LIB_PATH", "build", "lib", "Session", "WorkloadParams", "loss_threshold", "ge_thresholds",
            "fec_q16", "device_selftest", "cpu_share", "SUMMARY_FIELDS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtonk_amd.so")
+# The stateful batched compressor (include/tonk_compress_batch.h) is a library of its own beside it.
+CBATCH_LIB_PATH = os.path.join(_HERE, "libtonk_amd_cbatch.so")
 # A/B runs of two builds on one box (tools/gpu_ab.sh's LIB column): another in-tree build of the
 # library, by file name.
 if os.environ.get("TONK_AMD_LIB"):
     LIB_PATH = os.path.join(_HERE, os.path.basename(os.environ["TONK_AMD_LIB"]))
 _lib = None
+_others = {}  # the libraries beside the engine's, by path
 
 
 def build(jobs: int = 8) -> str:
@@ -33,9 +36,16 @@ def build(jobs: int = 8) -> str:
     return LIB_PATH
 
 
-def lib() -> ctypes.CDLL:
-    """Load the in-tree engine library.  Raises if it has not been built."""
+def lib(path: str | None = None) -> ctypes.CDLL:
+    """Load the in-tree engine library, or the library beside it at `path` (CBATCH_LIB_PATH).
+    Raises if it has not been built."""
     global _lib
+    if path is not None:
+        if path not in _others:
+            if not os.path.exists(path):
+                raise RuntimeError(f"tonk_amd: {path} missing -- run tonk_amd.build() (no CPU fallback exists)")
+            _others[path] = ctypes.CDLL(path, mode=ctypes.RTLD_LOCAL)
+        return _others[path]
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"tonk_amd: {LIB_PATH} missing -- run tonk_amd.build() (no CPU fallback exists)")
@@ -283,3 +293,9 @@ __all__.append("DatagramSealer")
 from .dgram import DatagramFramer  # noqa: E402
 
 __all__.append("DatagramFramer")
+
+# Stateful compression and decompression of messages in the caller's own device memory
+# (include/tonk_compress_batch.h).
+from .cbatch import BatchCompressor  # noqa: E402
+
+__all__.append("BatchCompressor")

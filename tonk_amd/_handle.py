@@ -1,4 +1,4 @@
-"""What the classes over the batched device interfaces share (batch.py, seal.py, dgram.py): the
+"""What the classes over the batched device interfaces share (batch.py, seal.py, dgram.py, cbatch.py): the
 ctypes prototypes of an interface bound once, the array marshalling, and the base class that owns a
 library handle -- creation, refusals, kernel timing and release.  The library's side of this is
 tonk_amd/csrc/handle.h."""
@@ -60,14 +60,14 @@ def ptr(a, t):
 class Handle:
     """A library handle of the interface `_PREFIX`, whose calls beside the common five are `_CALLS`
     (reached as self._c.<name>); `_REFUSED` names its negative return codes, `KERNEL_MS_FIELDS`
-    what kernel_ms returns."""
+    what kernel_ms returns; `_LIB` is the library's path when it is not the engine's."""
 
-    _PREFIX, _CALLS, _REFUSED, KERNEL_MS_FIELDS = "", {}, {}, ()
+    _PREFIX, _CALLS, _REFUSED, KERNEL_MS_FIELDS, _LIB = "", {}, {}, (), None
     _h = _c = None
 
     @classmethod
     def _bind(cls) -> SimpleNamespace:
-        return bind(_lib_loader(), cls._PREFIX, cls._CALLS)
+        return bind(_lib_loader(cls._LIB), cls._PREFIX, cls._CALLS)
 
     def _create(self, params: ctypes.Structure) -> None:
         self._c = self._bind()

@@ -1,4 +1,4 @@
-// handle.h -- what the batched device interfaces share (batch.cpp, seal.cpp, dgram.cpp): the
+// handle.h -- what the batched device interfaces share (batch.cpp, seal.cpp, dgram.cpp, cbatch.cpp): the
 // device check, the launch timer, the core of a handle (lock, device, stream, sticky error,
 // staging, one call's copy-launch-copy-wait) and the common parts of the C entry points.  A handle
 // type is a plain struct with a member `core`.
@@ -125,16 +125,21 @@ struct HandleCore {
     }
     template <class F>
     void launch_timed(int kind, F&& f) { timer.launch(*this, kind, f); }
-    // Upload `up` descriptor bytes, run `launch`, bring `down` result bytes back (none: no copy)
-    // and wait.
+    // Upload `up` descriptor bytes, let `enqueue` put the call's launches on the stream (each through
+    // launch_timed), bring `down` result bytes back (none: no copy) and wait.
     template <class F>
-    bool run(int kind, size_t up, size_t down, F&& launch) {
+    bool run_all(size_t up, size_t down, F&& enqueue) {
         if (!hip(hipMemcpyAsync(desc.dev, desc.host, up, hipMemcpyHostToDevice, stream), "descriptor copy")) return false;
-        launch_timed(kind, launch);
+        enqueue();
         if (down) hip(hipMemcpyAsync(out.host, out.dev, down, hipMemcpyDeviceToHost, stream), "result copy");
         hip(hipStreamSynchronize(stream), "hipStreamSynchronize");
         timer.collect();
         return !failed;
+    }
+    // The same for a call that is one launch.
+    template <class F>
+    bool run(int kind, size_t up, size_t down, F&& launch) {
+        return run_all(up, down, [&] { launch_timed(kind, launch); });
     }
     ~HandleCore() {
         if (device < 0) return;

@@ -44,6 +44,9 @@ typedef struct DgramFoot { uint64_t dst; uint32_t len, pad; uint8_t b[24]; } Dgr
    not walked.  DgramOut and up to `cap` table entries out each. */
 typedef struct DgramSect { uint64_t data; uint32_t bytes, skip; } DgramSect;
 typedef struct DgramOut { uint32_t status, count, rel_off, rel_bytes; } DgramOut;
+/* tamd_lz_place_ring (lz_place.hip): a stream's history ring (lz.h: TAMD_LZ_RING + TAMD_LZ_MIRROR
+   bytes), the caller's device address of a message, the ring offset it lands at and its bytes */
+typedef struct LzPlaceDesc { uint64_t ring, src; uint32_t slot, len; } LzPlaceDesc;
 
 static_assert(sizeof(GenDesc) == 24, "GenDesc");
 static_assert(sizeof(GatherDesc) == 12, "GatherDesc");
@@ -61,6 +64,7 @@ static_assert(sizeof(DgramMsg) == 24, "DgramMsg");
 static_assert(sizeof(DgramFoot) == 40, "DgramFoot");
 static_assert(sizeof(DgramSect) == 16, "DgramSect");
 static_assert(sizeof(DgramOut) == 16, "DgramOut");
+static_assert(sizeof(LzPlaceDesc) == 24, "LzPlaceDesc");
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -85,6 +89,7 @@ __global__ void tamd_seal_packets(const SealDesc*, uint32_t, const uint32_t*, ui
 __global__ void tamd_gather_footers(const TailDesc*, uint32_t, uint8_t*);
 __global__ void tamd_dgram_frames(const DgramMsg*, uint32_t, const DgramFoot*, uint32_t);
 __global__ void tamd_dgram_sections(const DgramSect*, uint32_t, uint32_t, uint32_t, DgramOut*, uint32_t*);
+__global__ void tamd_lz_place_ring(const LzPlaceDesc*, uint32_t);
 __global__ void tamd_timed_region();
 __global__ void tamd_nop();
 }
