@@ -15,13 +15,15 @@ import ctypes
 import os
 import subprocess
 
-__all__ = ["LIB_PATH", "CBATCH_LIB_PATH", "build", "lib", "Session", "WorkloadParams", "loss_threshold", "ge_thresholds",
+__all__ = ["LIB_PATH", "CBATCH_LIB_PATH", "RECV_LIB_PATH", "build", "lib", "Session", "WorkloadParams", "loss_threshold", "ge_thresholds",
            "fec_q16", "device_selftest", "cpu_share", "SUMMARY_FIELDS"]
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libtonk_amd.so")
 # The stateful batched compressor (include/tonk_compress_batch.h) is a library of its own beside it.
 CBATCH_LIB_PATH = os.path.join(_HERE, "libtonk_amd_cbatch.so")
+# So is the stateful receive front (include/tonk_receive.h).
+RECV_LIB_PATH = os.path.join(_HERE, "libtonk_amd_recv.so")
 # A/B runs of two builds on one box (tools/gpu_ab.sh's LIB column): another in-tree build of the
 # library, by file name.
 if os.environ.get("TONK_AMD_LIB"):
@@ -37,7 +39,7 @@ def build(jobs: int = 8) -> str:
 
 
 def lib(path: str | None = None) -> ctypes.CDLL:
-    """Load the in-tree engine library, or the library beside it at `path` (CBATCH_LIB_PATH).
+    """Load the in-tree engine library, or the library beside it at `path` (CBATCH_LIB_PATH, RECV_LIB_PATH).
     Raises if it has not been built."""
     global _lib
     if path is not None:
@@ -299,3 +301,9 @@ __all__.append("DatagramFramer")
 from .cbatch import BatchCompressor  # noqa: E402
 
 __all__.append("BatchCompressor")
+
+# Nonce expansion, anti-replay and open of received datagrams in the caller's own device memory
+# (include/tonk_receive.h).
+from .recv import DatagramReceiver  # noqa: E402
+
+__all__.append("DatagramReceiver")

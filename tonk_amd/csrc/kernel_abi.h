@@ -1,5 +1,5 @@
 // kernel_abi.h -- the records the helper kernels of kernels.hip read and write, and the
-// prototypes of every kernel the host launches (device.cpp, server.cpp, batch.cpp, seal.cpp): one definition for both
+// prototypes of every kernel the host launches (device.cpp, server.cpp, batch.cpp, seal.cpp, recv.cpp): one definition for both
 // sides.  The records are plain C; the prototypes need a HIP translation unit.
 #pragma once
 #include <stdint.h>
@@ -47,6 +47,34 @@ typedef struct DgramOut { uint32_t status, count, rel_off, rel_bytes; } DgramOut
 /* tamd_lz_place_ring (lz_place.hip): a stream's history ring (lz.h: TAMD_LZ_RING + TAMD_LZ_MIRROR
    bytes), the caller's device address of a message, the ring offset it lands at and its bytes */
 typedef struct LzPlaceDesc { uint64_t ring, src; uint32_t slot, len; } LzPlaceDesc;
+/* the kernels of recv.hip: one RecvDesc per datagram of a call (the caller's device address, the
+   row of the key table and of the anti-replay state, total bytes).  tamd_rx_parse writes a
+   RecvFields each (flags 0: an invalid datagram, nothing else meaningful); tamd_rx_resolve a
+   RecvResult each, include/tonk_receive.h's tamd_recv_result.  RecvCall is the argument of all
+   five kernels: the records, the call's streams as a CSR list (stream listed[j] owns items
+   idx[start[j] .. start[j + 1]) in list order), what the steps hand on (the predicted nonces, the
+   tag verdicts under them, the bytes to decipher), the handle's state and key tables and its three
+   guard blocks with where their copy goes. */
+typedef struct RecvDesc { uint64_t data; uint32_t stream, bytes; } RecvDesc;
+typedef struct RecvFields { uint32_t partial_nonce, partial_seq, ts24; uint8_t flags, seq_bytes, nonce_bytes, handshake_bytes; } RecvFields;
+typedef struct RecvResult {
+    uint64_t nonce;
+    uint32_t message_bytes, timestamp24, partial_seq;
+    uint8_t flags, seq_bytes, nonce_bytes, handshake_bytes;
+} RecvResult;
+typedef struct RecvCall {
+    const RecvDesc* d;
+    const uint32_t *listed, *start, *idx;
+    RecvFields* f;
+    uint64_t* pred;
+    uint32_t *tag_ok, *rc, *clen;
+    RecvResult* res;
+    uint64_t* state;
+    const uint32_t* keys;
+    const uint8_t* guard[3];
+    uint8_t* guards_out;
+    uint32_t n, n_listed, max_bytes, pad;
+} RecvCall;
 
 static_assert(sizeof(GenDesc) == 24, "GenDesc");
 static_assert(sizeof(GatherDesc) == 12, "GatherDesc");
@@ -65,6 +93,9 @@ static_assert(sizeof(DgramFoot) == 40, "DgramFoot");
 static_assert(sizeof(DgramSect) == 16, "DgramSect");
 static_assert(sizeof(DgramOut) == 16, "DgramOut");
 static_assert(sizeof(LzPlaceDesc) == 24, "LzPlaceDesc");
+static_assert(sizeof(RecvDesc) == 16, "RecvDesc");
+static_assert(sizeof(RecvFields) == 16, "RecvFields");
+static_assert(sizeof(RecvResult) == 24, "RecvResult");
 
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -90,6 +121,11 @@ __global__ void tamd_gather_footers(const TailDesc*, uint32_t, uint8_t*);
 __global__ void tamd_dgram_frames(const DgramMsg*, uint32_t, const DgramFoot*, uint32_t);
 __global__ void tamd_dgram_sections(const DgramSect*, uint32_t, uint32_t, uint32_t, DgramOut*, uint32_t*);
 __global__ void tamd_lz_place_ring(const LzPlaceDesc*, uint32_t);
+__global__ void tamd_rx_parse(const RecvCall);
+__global__ void tamd_rx_predict(const RecvCall);
+__global__ void tamd_rx_tag(const RecvCall);
+__global__ void tamd_rx_resolve(const RecvCall);
+__global__ void tamd_rx_decipher(const RecvCall);
 __global__ void tamd_timed_region();
 __global__ void tamd_nop();
 }
