@@ -11,10 +11,13 @@
 //                   (streams stream..stream+S-1 concurrently on T threads, one codec pair each;
 //                    <prefix><id>.txt per stream -- the C ABI's concurrent-codec check)
 //        golden_gen time threads=T streams=S reps=R key=value...
+//        golden_gen impaired <out.txt> key=value...
+//                   (the impaired channel of oracle/impaired.h: its keys beside the workload's)
 #include "siamese.h"
 
 #include "../tonk_amd/csrc/workload.h"
 #include "../tonk_amd/csrc/transcript.h"
+#include "impaired.h"
 
 #include <algorithm>
 #include <chrono>
@@ -262,6 +265,17 @@ struct RefTranscript {
     }
 };
 
+// The backend of the `impaired` command: a recovery packet can be handed over twice.
+struct ImpRefBackend : RefBackend {
+    explicit ImpRefBackend(const Params& prm) : RefBackend(prm) {}
+    RecRef rec_copy(const RecRef& r) { return r; }
+    uint32_t rec_end(const RecRef& r) {
+        RefTranscript::RecoveryMetadataView m;
+        RefTranscript::decode_footer(r.bytes, m);
+        return m.cs + m.sc;
+    }
+};
+
 static uint32_t g_pool = 0;  // time mode: payload pool per stream (RefBackend::pool)
 static int g_runs = 1;        // time mode: timed passes
 static bool parse_kv(Params& p, int& threads, int& streams, int& reps, const char* kv) {
@@ -292,9 +306,13 @@ int main(int argc, char** argv) {
     int threads = 1, streams = 1, reps = 1;
     const bool timing = strcmp(argv[1], "time") == 0;
     const bool multi = strcmp(argv[1], "transcripts") == 0;
+    const bool impaired = strcmp(argv[1], "impaired") == 0;
+    Impair imp;
     const int first_kv = timing ? 2 : 3;
     if (!timing && argc < 3) { fprintf(stderr, "missing output path\n"); return 2; }
     for (int i = first_kv; i < argc; ++i) {
+        const char* eq = strchr(argv[i], '=');
+        if (impaired && eq && parse_impair(imp, std::string(argv[i], eq - argv[i]), strtoull(eq + 1, nullptr, 0))) continue;
         if (!parse_kv(base, threads, streams, reps, argv[i])) { fprintf(stderr, "bad arg %s\n", argv[i]); return 2; }
     }
 
@@ -313,6 +331,14 @@ int main(int argc, char** argv) {
         fclose(f);
         return true;
     };
+    if (impaired) {
+        if (base.hold_full) { fprintf(stderr, "impaired: full=1 is not supported\n"); return 2; }
+        ImpRefBackend be(base);
+        RefTranscript tr;
+        const Summary s = run_impaired(base, imp, be, tr);
+        if (!write_transcript(argv[2], tr, s, be.bad_recoveries)) return 4;
+        return be.bad_recoveries ? 5 : 0;
+    }
     if (multi) {
         std::atomic<int> next{0};
         std::atomic<unsigned long long> bad{0};

@@ -6,12 +6,14 @@
 // pin the control plane (every decision and every recovery/recovered byte) on CPU-only hosts.
 //
 // usage: cp_harness <out.txt> mode=sync|batch batch=K key=value...
+//        impaired=1 and the keys of oracle/impaired.h: the stream runs through the impaired channel
 #include "../../tonk_amd/csrc/encoder.h"
 #include "../../tonk_amd/csrc/decoder.h"
 #include "../../tonk_amd/csrc/workload.h"
 #include "../../tonk_amd/csrc/transcript.h"
 #include "../../tonk_amd/csrc/prof.h"
 #include "../../oracle/siamese_oracle.h"
+#include "../../oracle/impaired.h"
 
 #include <chrono>
 #include <stdio.h>
@@ -494,6 +496,18 @@ struct Harness {
         return rc;
     }
     void recovery_lost(const RecRef& r) { ctx.rows.free_deferred(r.out.row); }
+    // (impaired channel) A recovery packet handed over twice cannot be the same row twice (the
+    // decoder may have taken the first): a second row holding the same bytes, copied within the
+    // arena once the packet's program has run.  The flush changes batching, not the transcript.
+    RecRef rec_copy(const RecRef& r) {
+        flush();
+        RecRef c = r;
+        c.out.row = ctx.alloc(r.out.total());
+        if (c.out.row == kNoRow) { error = "arena full"; return r; }
+        memcpy(at(c.out.row), at(r.out.row), r.out.total());
+        return c;
+    }
+    uint32_t rec_end(const RecRef& r) const { return r.out.meta.ColumnStart + r.out.meta.SumCount; }
 
     int dec_add_recovery(const RecRef& r) {
         bool took = false;
@@ -574,6 +588,8 @@ int main(int argc, char** argv) {
     if (!gf_init()) { fprintf(stderr, "gf_init failed\n"); return 3; }
     if (oracle_self_test() != 0) { fprintf(stderr, "oracle self test failed\n"); return 3; }
     Params p;
+    Impair imp;
+    bool impaired = false;
     bool sync = true;
     uint32_t batch = 0;
     for (int i = 2; i < argc; ++i) {
@@ -596,13 +612,15 @@ int main(int argc, char** argv) {
         else if (k == "ahead") g_ahead = (uint32_t)v;
         else if (k == "short") g_short = v != 0;
         else if (k == "ddirect") g_ddirect = (int)v;
-        else if (parse_param(p, k, v)) {}
+        else if (k == "impaired") impaired = v != 0;
+        else if (parse_param(p, k, v) || parse_impair(imp, k, v)) {}
         else { fprintf(stderr, "bad key %s\n", k.c_str()); return 2; }
     }
     Harness h(p);
     h.sync = sync;
     h.batch = sync ? 0 : (batch ? batch : 1u << 30);
-    Summary s = run_stream(p, h, h);
+    if (impaired && (p.hold_full || g_contig)) { fprintf(stderr, "impaired: full=1 and contig=1 are not supported\n"); return 2; }
+    Summary s = impaired ? run_impaired(p, imp, h, h) : run_stream(p, h, h);
     h.flush();
     FILE* f = fopen(argv[1], "wb");
     if (!f) return 4;

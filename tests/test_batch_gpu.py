@@ -432,3 +432,230 @@ def test_full_arena_disables_one_stream(hip):
     finally:
         bc.close()
         ref.close()
+
+
+# ---- reordering, duplicates and stale acknowledgements ----
+
+IMP_ORIG, IMP_TICK, IMP_REC = 96, 8, 2
+
+
+def impaired_lengths(s):
+    """1300 for even streams, LENS18 rotated for odd ones."""
+    return [1300] * IMP_ORIG if s % 2 == 0 else ((LENS18[s % 18:] + LENS18[:s % 18]) * 6)[:IMP_ORIG]
+
+
+_scripts = {}
+
+
+def impaired_decoder_script(n_streams):
+    """The reference's side of test_decoder_under_impairment, computed once per stream count: the
+    calls of a seeded delivery plan in order, each with what RefDecoder returned.  5 % of the
+    originals are lost; 25 % of the delivered packets of either kind are held for 1-3 ticks; 10 %
+    are delivered twice (the second copy 0-2 ticks after the first); stream 0's whole first tick of
+    originals is held, so its first recovery packet meets an empty decoder.  The senders
+    (RefEncoder) get their receiver's acknowledgement every third tick.
+    Steps: ("orig", [(stream, num, payload)], rcs), ("rec", [(stream, packet)], rcs),
+    ("decode", [(rc, [(num, payload)])] per stream), ("ack", [(rc, bytes)] per stream)."""
+    if n_streams in _scripts:
+        return _scripts[n_streams]
+    rng = np.random.default_rng(4100 + n_streams)
+    pay = make_payloads(n_streams, impaired_lengths, 21)
+    encs = [RefEncoder() for _ in range(n_streams)]
+    decs = [RefDecoder() for _ in range(n_streams)]
+    n_ticks = IMP_ORIG // IMP_TICK
+    arrive_o = [[] for _ in range(n_ticks + 8)]
+    arrive_r = [[] for _ in range(n_ticks + 8)]
+    steps, stats = [], {"duplicate": 0, "recovered": 0, "behind": 0, "late_originals": 0}
+    newest = [-1] * n_streams  # encode sequence of the newest recovery packet delivered
+    n_encoded = [0] * n_streams
+
+    def fate(force_hold=False, never_hold=False):
+        u = rng.random(5)
+        hold = 1 + int(u[2] * 3) if u[1] < 0.25 else 0
+        if force_hold:
+            hold = max(hold, 1)
+        if never_hold:
+            hold = 0
+        return u[0] < 0.05, hold, (hold + int(u[4] * 3) if u[3] < 0.10 else None)
+
+    def decode_step():
+        want = [d.decode_if_ready() for d in decs]
+        stats["recovered"] += sum(len(w[1]) for w in want)
+        steps.append(("decode", want))
+
+    def deliver(t):
+        if arrive_o[t]:
+            ent = arrive_o[t]
+            rcs = [decs[s].add_original(i, pay[s][i]) for s, i in ent]
+            stats["duplicate"] += rcs.count(DUPLICATE)
+            steps.append(("orig", [(s, i, pay[s][i]) for s, i in ent], rcs))
+            decode_step()
+        if arrive_r[t]:
+            ent = arrive_r[t]
+            rcs = []
+            for s, seq, data in ent:
+                if seq < newest[s]:
+                    stats["behind"] += 1
+                newest[s] = max(newest[s], seq)
+                rcs.append(decs[s].add_recovery(data))
+            steps.append(("rec", [(s, data) for s, _, data in ent], rcs))
+            decode_step()
+        acks = [d.ack() for d in decs]
+        steps.append(("ack", acks))
+        if t % 3 == 2:
+            for s, (arc, ack) in enumerate(acks):
+                if arc == 0 and ack:
+                    assert encs[s].ack(ack)[0] == 0
+
+    def send_recovery(s, t, in_order):
+        rc, data = encs[s].encode()
+        _, hold, dup = fate(never_hold=in_order)
+        if rc != 0:  # (everything acknowledged: the sender has nothing to protect)
+            assert rc == NEED_MORE and t >= n_ticks
+            return
+        arrive_r[t + hold].append((s, n_encoded[s], data))
+        if dup is not None and not in_order:
+            arrive_r[t + dup].append((s, n_encoded[s], data))
+        n_encoded[s] += 1
+
+    for t in range(n_ticks):
+        for k in range(IMP_TICK):
+            for s in range(n_streams):
+                i = t * IMP_TICK + k
+                assert encs[s].add(pay[s][i]) == (0, i)
+                lost, hold, dup = fate(force_hold=(s == 0 and t == 0))
+                if lost:
+                    continue
+                stats["late_originals"] += hold > 0
+                arrive_o[t + hold].append((s, i))
+                if dup is not None:
+                    arrive_o[t + dup].append((s, i))
+        for s in range(n_streams):
+            for _ in range(IMP_REC):
+                send_recovery(s, t, in_order=(s == 0 and t == 0))
+        deliver(t)
+    for t in range(n_ticks, n_ticks + 6):  # what is still held, then recovery packets in order
+        for s in range(n_streams):
+            for _ in range(IMP_REC):
+                send_recovery(s, t, in_order=True)
+        deliver(t)
+    for x in encs + decs:
+        x.close()
+    _scripts[n_streams] = (steps, stats)
+    return _scripts[n_streams]
+
+
+class Recorded:
+    """A RefDecoder's recorded answer, for decode_and_compare."""
+
+    def __init__(self, result):
+        self.result = result
+
+    def decode_if_ready(self):
+        return self.result
+
+
+@pytest.mark.parametrize("n_streams", [3, 8])
+def test_decoder_under_impairment(hip, n_streams):
+    """The batched decoder at 3 and at 8 streams (the two configurations of tamd_batch_create: back
+    substitution over materialized rows and short scans up to 4 streams, split dense ranges above)
+    under reordering and duplication: every decoder_add_original, decoder_add_recovery, decode and
+    decoder_ack equals RefDecoder's, call by call, recovered payloads byte for byte."""
+    steps, stats = impaired_decoder_script(n_streams)
+    # (from the reference's returns: the comparison is not vacuous)
+    assert stats["duplicate"] >= 1 and stats["recovered"] >= 10 and stats["behind"] >= 1 and stats["late_originals"] >= 1
+    pitch = 4001
+    rec_pitch = pitch + OVER
+    most_o = max(len(st[1]) for st in steps if st[0] == "orig")
+    most_r = max(len(st[1]) for st in steps if st[0] == "rec")
+    bc = new_codec(n_streams, MAXB, n_streams * (32 << 20))
+    src = Guarded(hip, most_o * pitch, 1)
+    rec = Guarded(hip, most_r * rec_pitch, 2)
+    out = Guarded(hip, 64 * pitch, 7)
+    try:
+        for n, st in enumerate(steps):
+            if st[0] == "orig":
+                ent = st[1]
+                src.upload(slots([e[2] for e in ent], pitch))
+                rc = bc.decoder_add_original([e[0] for e in ent], [e[1] for e in ent], [len(e[2]) for e in ent], src.ptr, pitch)
+                assert list(rc) == st[2], f"step {n}"
+            elif st[0] == "rec":
+                ent = st[1]
+                rec.upload(slots([e[1] for e in ent], rec_pitch))
+                rc = bc.decoder_add_recovery([e[0] for e in ent], [len(e[1]) for e in ent], rec.ptr, rec_pitch)
+                assert list(rc) == st[2], f"step {n}"
+            elif st[0] == "decode":
+                decode_and_compare(bc, [Recorded(w) for w in st[1]], out, pitch, 64, f"step {n}")
+            else:
+                assert [bc.decoder_ack(s) for s in range(n_streams)] == st[1], f"step {n}"
+            check_all(src, rec, out)
+    finally:
+        bc.close()
+
+
+def test_encoder_under_impairment(hip):
+    """One batched encoder per stream beside a RefEncoder, fed the same originals and the same
+    acknowledgements out of a seeded plan: 30 % dropped, 30 % held for one or two ticks (delivered
+    oldest-due first, so a held one arrives after a newer one: the stale acknowledgement), 20 %
+    delivered twice in succession.  The acknowledgements are a RefDecoder's that lost 5 % of the
+    originals.  encoder_ack's results and the bytes of every later encode must be equal."""
+    n_streams, pitch = 2, 4001
+    out_pitch = pitch + OVER
+    rng = np.random.default_rng(77)
+    pay = make_payloads(n_streams, impaired_lengths, 31)
+    bc = new_codec(n_streams, MAXB, 64 << 20)
+    encs = [RefEncoder() for _ in range(n_streams)]
+    decs = [RefDecoder() for _ in range(n_streams)]
+    src = Guarded(hip, n_streams * IMP_TICK * pitch, 3)
+    out = Guarded(hip, n_streams * IMP_REC * out_pitch, 5)
+    pending, newest = [], [-1] * n_streams
+    dropped = stale = repeated = 0
+    try:
+        for t in range(IMP_ORIG // IMP_TICK):
+            ent = [(s, t * IMP_TICK + k) for k in range(IMP_TICK) for s in range(n_streams)]
+            pk = [pay[s][i] for s, i in ent]
+            src.upload(slots(pk, pitch))
+            pn, rc = bc.encoder_add([e[0] for e in ent], [len(p) for p in pk], src.ptr, pitch)
+            want = [encs[s].add(p) for (s, _), p in zip(ent, pk)]
+            assert list(rc) == [w[0] for w in want] and list(pn) == [w[1] for w in want], t
+            elist = [s for s in range(n_streams) for _ in range(IMP_REC)]
+            out.fill()
+            nb, rc = bc.encode(elist, out.ptr, out_pitch)
+            want = [encs[s].encode() for s in elist]
+            assert list(rc) == [w[0] for w in want] == [0] * len(elist), t
+            assert list(nb) == [len(w[1]) for w in want], t
+            for j, (g, w) in enumerate(zip(recovery_slots(out, out_pitch, nb), want)):
+                assert g == w[1], f"tick {t}: recovery packet {j} (stream {elist[j]}) differs"
+            check_all(src, out)
+            # the receivers (reference only), and their acknowledgements' way back
+            for (s, i), p in zip(ent, pk):
+                if rng.random() >= 0.05:
+                    assert decs[s].add_original(i, p) == 0
+            for s, w in zip(elist, want):
+                assert decs[s].add_recovery(w[1]) == 0
+            for d in decs:
+                d.decode_if_ready()
+            for s in range(n_streams):
+                arc, ack = decs[s].ack()
+                u = rng.random(4)
+                if arc != 0 or not ack:
+                    continue
+                if u[0] < 0.30:
+                    dropped += 1
+                    continue
+                hold = 1 + int(u[2] * 2) if u[1] < 0.30 else 0
+                pending.append((t + hold, t, s, ack, bool(u[3] < 0.20)))
+            due = sorted(x for x in pending if x[0] <= t)
+            pending = [x for x in pending if x[0] > t]
+            for _, seq, s, ack, twice in due:
+                if seq < newest[s]:
+                    stale += 1
+                newest[s] = max(newest[s], seq)
+                for _ in range(2 if twice else 1):
+                    assert bc.encoder_ack(s, ack) == encs[s].ack(ack), (t, s, seq)
+                repeated += twice
+        assert dropped >= 1 and stale >= 1 and repeated >= 1
+    finally:
+        bc.close()
+        for x in encs + decs:
+            x.close()

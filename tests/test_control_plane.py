@@ -180,3 +180,144 @@ def test_control_plane_long_streams(harness, golden_index, tmp_path, name, mode)
     text = out.read_text()
     assert text.splitlines()[-1] == e["summary"]
     assert hashlib.sha256(text.encode()).hexdigest() == e["sha256"]
+
+
+# ---- the impaired channel (oracle/impaired.h): reordering, duplicates, lost / stale / repeated acks ----
+
+IMPAIRED = ["imp_near", "imp_far", "imp_recfirst", "imp_var_dup", "imp_acks", "imp_burst_arq", "imp_rtx", "imp_all",
+            "imp_clip"]
+IMP_SEEDS = ["seed_data=1000", "seed_loss=2000"]
+# the C ABI's per-call mode, plain per-call programs, and the batched session's pipelined mode with its
+# hazard checks on (contig=1 is the in-order Session's layout and is left out)
+IMP_MODES = {"capi": ["mode=sync", "dirty=1", "expand=16", "backsub=2", "ahead=15", "short=1"],
+             "sync": ["mode=sync"],
+             "batch-pipe": ["mode=batch", "batch=1000", "pipeline=1", "drain=2", "split=48"]}
+
+
+@pytest.fixture(scope="module")
+def impaired_index():
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "impaired.json")) as f:
+        return json.load(f)["scenarios"]
+
+
+@pytest.mark.parametrize("name", ["c1_256_p3", "var_1_1500_p2_ack32", "hiloss_p20_arq", "rtx_p5_ack32", "burst8_p5"])
+def test_impaired_driver_without_impairments_is_the_old_driver(harness, golden_index, tmp_path, name):
+    """With every impairment zero the impaired-channel driver makes Runner's calls: through it the
+    control plane writes exactly the existing golden transcripts (this ties the new driver to the
+    old one without the reference)."""
+    sc = golden_index["scenarios"][name]
+    sid = sc["stream"]
+    out = tmp_path / "t.txt"
+    r = subprocess.run([harness, str(out), "mode=sync", "impaired=1"] + sc["args"] +
+                       [f"seed_data={1000 + sid}", f"seed_loss={2000 + sid}"], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    want = golden_text(name)
+    assert out.read_text() == want, first_diff(want, out.read_text())
+
+
+@pytest.mark.parametrize("name,mode", [(n, m) for n in IMPAIRED for m in IMP_MODES] +
+                         [("imp_far", "lanes"), ("imp_all", "lanes")])
+def test_control_plane_impaired_matches_reference(harness, impaired_index, tmp_path, name, mode):
+    """Every impaired fixture (late and duplicate originals and recovery packets, dropped, stale and
+    repeated acknowledgements; tests/golden/impaired.json) through the control plane: transcript ==
+    the reference codec's, bit for bit.  "lanes": eliminations through the lane sums only
+    (ddirect=0), for the two scenarios whose packets arrive furthest out of order."""
+    margs = ["mode=sync", "ddirect=0"] if mode == "lanes" else IMP_MODES[mode]
+    sc = impaired_index[name]
+    out = tmp_path / "t.txt"
+    r = subprocess.run([harness, str(out), "impaired=1"] + margs + sc["args"] + IMP_SEEDS,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    want = golden_text(name)
+    assert out.read_text() == want, first_diff(want, out.read_text())
+
+
+def test_control_plane_impaired_vs_reference_build(harness, impaired_index, tmp_path):
+    """imp_all's parameters on seeds 1..8 against transcripts the reference build
+    (oracle/_ref/golden_gen impaired) writes on the spot, in the C ABI's mode and the batched one."""
+    exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "golden_gen")
+    if not os.path.exists(exe):
+        pytest.skip("reference build absent (oracle/_ref)")
+    # a reference build made before the driver had this command is brought up to date (oracle/Makefile
+    # rebuilds golden_gen when its sources' contents changed), never skipped
+    probe = [exe, "impaired", os.devnull, "n=1", "reorder=0"]
+    if subprocess.run(probe, capture_output=True).returncode != 0:
+        _make(os.path.dirname(os.path.dirname(exe)), "ref")
+        r = subprocess.run(probe, capture_output=True, text=True)
+        assert r.returncode == 0, "oracle/_ref/golden_gen is older than oracle/golden_gen.cpp: " + r.stderr[-500:]
+    base = [a for a in impaired_index["imp_all"]["args"] if not a.startswith("seed_impair=")]
+    for s in range(1, 9):
+        args = base + [f"seed_data={1000 + s}", f"seed_loss={2000 + s}", f"seed_impair={3000 + s}"]
+        ref = tmp_path / "r.txt"
+        r = subprocess.run([exe, "impaired", str(ref)] + args, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        want = ref.read_text()
+        for m in (IMP_MODES["capi"], IMP_MODES["batch-pipe"]):
+            out = tmp_path / "o.txt"
+            r = subprocess.run([harness, str(out), "impaired=1"] + m + args, capture_output=True, text=True, timeout=600)
+            assert r.returncode == 0, r.stderr[-2000:]
+            assert out.read_text() == want, f"seed {s} {m}: " + first_diff(want, out.read_text())
+
+
+def test_impaired_fixtures_hold_the_cases(impaired_index):
+    """The fixtures themselves (the reference's own lines, nothing run here) contain what they are
+    there for.  Event lines of oracle/impaired.h: `H copy col rc` an original arriving late (copy 2:
+    a second copy), `Q copy behind rc` a recovery packet arriving late (behind: its ColumnStart +
+    SumCount lies below an earlier delivered one's), `L` a dropped, `V` a stale, `P` a repeated
+    acknowledgement; `X` / `T` lines are ARQ and retransmitted originals with a non-zero result."""
+    import hashlib
+    DUPLICATE = 4
+    refused = accepted = behind_used = behind_idle = dropped = stale = repeated = multi_after_late = 0
+    duped_recovery_scenarios = 0
+    summaries = {}
+    for name in IMPAIRED:
+        sc = impaired_index[name]
+        text = golden_text(name)
+        assert hashlib.sha256(text.encode()).hexdigest() == sc["sha256"], name
+        lines = [ln.split() for ln in text.splitlines()]
+        assert " ".join(lines[-1]) == sc["summary"] and lines[-1][0] == "Z"
+        summaries[name] = dict(kv.split("=") for kv in lines[-1][1:])
+        for i, f in enumerate(lines):
+            nxt = lines[i + 1] if i + 1 < len(lines) else ["-"]
+            if f[0] == "H":
+                refused += int(f[3]) == DUPLICATE
+                accepted += f[1] == "1" and f[3] == "0"
+            elif f[0] in "XT" and len(f) == 4 and f[1] == str(DUPLICATE):
+                refused += 1
+            elif f[0] == "Q" and f[2] == "1" and f[3] == "0":
+                # a late row that completes a solve is used by it; one followed by no decode is not (yet)
+                if nxt[0] == "D" and nxt[1] == "0" and int(nxt[2]) >= 1:
+                    behind_used += 1
+                elif nxt[0] != "D":
+                    behind_idle += 1
+            dropped += f[0] == "L"
+            stale += f[0] == "V"
+            repeated += f[0] == "P"
+            if f[0] in "HQ" and nxt[0] == "D" and nxt[1] == "0" and int(nxt[2]) >= 2:
+                multi_after_late += 1
+        stats = [f for f in lines if f[0] == "S"]
+        assert len(stats) == 1
+        dec = stats[0][stats[0].index("|") + 1:]
+        duped_recovery_scenarios += int(dec[9]) > 0  # SiameseDecoderStats_DupedRecoveryCount
+    assert refused > 0 and accepted > 0
+    assert behind_used > 0 and behind_idle > 0
+    assert duped_recovery_scenarios >= 4
+    assert dropped > 0 and stale > 0 and repeated > 0
+    assert multi_after_late > 0
+    # imp_recfirst: its first originals are all lost or held (they arrive as H lines), so every
+    # recovery packet encoded before the first H line that the channel did not lose met a decoder
+    # that had seen no original -- and more were encoded than the channel lost in the whole stream
+    rf = [ln.split() for ln in golden_text("imp_recfirst").splitlines()]
+    hold = int(dict(a.split("=") for a in impaired_index["imp_recfirst"]["args"])["hold_first"])
+    first_h = next(i for i, f in enumerate(rf) if f[0] == "H")
+    early = sum(1 for f in rf[:first_h] if f[0] == "E" and f[1] == "0")
+    assert hold > 0 and early > int(summaries["imp_recfirst"]["lostrec"])
+    # the reference recovers what it is sent: nothing wrong anywhere, and at least six of the
+    # first eight scenarios end with nothing missing
+    assert all(s["bad"] == "0" for s in summaries.values())
+    assert sum(summaries[n]["missing"] == "0" for n in IMPAIRED[:8]) >= 6
+    for name in IMPAIRED:
+        assert impaired_index[name]["decoder_disabled"] == any(
+            ln.split()[:2] in (["D", "5"], ["O", "5"], ["R", "5"]) or (ln[0] in "HQ" and ln.split()[3] == "5")
+            for ln in golden_text(name).splitlines()), name

@@ -369,3 +369,26 @@ def test_capi_ring_passes_a_stalled_post(golden_index, tmp_path):
     bad = [s for s in range(16)
            if hashlib.sha256(open(f"{prefix}{s}.txt", "rb").read()).hexdigest() != entry["streams"][str(s)]["sha256"]]
     assert not bad, f"streams differing from the reference: {bad}"
+
+
+IMPAIRED = ["imp_near", "imp_far", "imp_recfirst", "imp_var_dup", "imp_acks", "imp_burst_arq", "imp_rtx", "imp_all",
+            "imp_clip"]
+
+
+@pytest.mark.parametrize("name", IMPAIRED)
+def test_capi_impaired_matches_reference(name):
+    """The siamese.h C ABI under the impaired channel (oracle/impaired.h: originals and recovery
+    packets late and twice, acknowledgements dropped, stale and repeated): `capi_gen impaired`
+    writes the reference codec's transcript (tests/golden/impaired.json), bit for bit."""
+    import json
+    exe = os.path.join(NATIVE, "_build", "capi_gen")
+    assert os.path.exists(exe), "build tests/native first (make -C tests/native)"
+    with open(os.path.join(ROOT, "tests", "golden", "impaired.json")) as f:
+        sc = json.load(f)["scenarios"][name]
+    out = subprocess.run([exe, "impaired", "/dev/stdout"] + sc["args"] + ["seed_data=1000", "seed_loss=2000"],
+                         capture_output=True, timeout=600)
+    assert out.returncode == 0, out.stderr.decode()[-2000:]
+    got = out.stdout.decode()
+    want = golden_text(name)
+    assert sha256(want) == sc["sha256"]
+    assert got == want, first_diff(want, got)
