@@ -11,7 +11,8 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF = os.path.join(ROOT, "oracle", "_ref", "libsiamese_ref.so")
 
-# the framing checks' lengths (tests/native/frame_check.cpp); the parity tests use the first 18 (through 4000)
+# the framing checks' lengths (tests/native/frame_check.cpp); the short-packet parity tests use the first 18
+# (through 4000), the long-packet ones their own list up to 65535 (test_batch_gpu.py LONG_LENS)
 LENGTHS = [1, 2, 15, 16, 17, 63, 64, 127, 128, 129, 1023, 1024, 1025, 1300, 1535, 1536, 1537, 4000, 16383, 16384, 65535]
 SUCCESS, INVALID, NEED_MORE, MAX_PACKETS, DUPLICATE, DISABLED = range(6)
 

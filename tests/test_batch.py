@@ -1,8 +1,8 @@
 """CPU checks of the batched codecs over the caller's device packets (include/tonk_batch.h):
 the header and the library's exports, the refusal to run without an MI355X, parameter checks that
 come before any device call, and the byte logic of the framing kernels (tonk_amd/csrc/frame.h) as
-a serial host walk -- tests/native/frame_check.cpp, plain and under the address and
-undefined-behaviour sanitizers, each a stand-alone program."""
+a host walk over 1, 64, 128 and 256 lanes -- tests/native/frame_check.cpp, plain and under the
+address and undefined-behaviour sanitizers, each a stand-alone program."""
 from __future__ import annotations
 
 import ctypes
@@ -130,14 +130,16 @@ def expected_rows():
 @pytest.mark.parametrize("which", ["frame_check", "frame_check_san"])
 def test_frame_logic_on_the_host(which, tmp_path):
     """The stand-alone walk, plain and with the sanitizers linked in: header round trips for every
-    length 1..70000, framing and unframing over the lengths x source misalignments 0..15, the
-    rejections with nothing written; its headers and framed rows against the oracle's."""
+    length 1..70000, framing and unframing over the lengths x source misalignments 0..15 with one
+    lane and with the 64, 128 and 256 lanes of one, two and four waves, the rejections with nothing
+    written, every byte written by exactly one lane, the launch shape's (packet, lane) cover; its
+    headers and framed rows against the oracle's."""
     exe = frame_check(which)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     print(r.stdout[-2000:])
     assert r.returncode == 0 and r.stdout.startswith("ok "), r.stdout[-2000:] + r.stderr[-4000:]
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr[-4000:]
-    assert int(r.stdout.split()[1]) >= len(LENS) * 16
+    assert int(r.stdout.split()[1]) >= 4 * len(LENS) * 16 + 15  # (four lane counts; 3 x 5 launch shapes)
 
     path = str(tmp_path / "headers.bin")
     r = subprocess.run([exe, "headers", path], capture_output=True, text=True, timeout=300)

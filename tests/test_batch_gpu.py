@@ -46,13 +46,12 @@ def payloads():
     return make_payloads(N_STREAMS, stream_lengths, 7)
 
 
-@pytest.fixture(scope="module")
-def ref_traffic(payloads):
-    """The reference encoders' traffic for the three streams, computed once: per round and
-    stream the recovery packets of ENCODE_LIST, then six more per stream at the end."""
+def reference_traffic(payloads, n_orig):
+    """The reference encoders' traffic for the three streams: per round and stream the recovery
+    packets of ENCODE_LIST, then six more per stream at the end."""
     encs = [RefEncoder() for _ in range(N_STREAMS)]
     rounds = []
-    for r in range(N_ORIG // PER_CALL):
+    for r in range(n_orig // PER_CALL):
         for s in range(N_STREAMS):
             for k in range(PER_CALL):
                 rc, pn = encs[s].add(payloads[s][r * PER_CALL + k])
@@ -73,6 +72,12 @@ def ref_traffic(payloads):
     for e in encs:
         e.close()
     return rounds
+
+
+@pytest.fixture(scope="module")
+def ref_traffic(payloads):
+    """(computed once)"""
+    return reference_traffic(payloads, N_ORIG)
 
 
 def new_codec(n_streams=N_STREAMS, maxb=MAXB, arena=96 << 20):
@@ -659,3 +664,295 @@ def test_encoder_under_impairment(hip):
         bc.close()
         for x in encs + decs:
             x.close()
+
+
+# ---- packets above 4096 bytes: two and four waves per packet, the 3-byte length header ----
+
+LONG_MAXB = 65535
+LONG_LENS = [1, 4093, 4094, 4097, 9000, 16381, 16382, 16383, 16384, 16385, 40000, 65534, 65535]
+LONG_ORIG = 36
+STREAM_ARENA = 64 << 20  # a stream's share: no codec disables itself for lack of rows
+# (payload slots, recovery slots): odd and minimal, then a multiple of 64 that holds either
+LONG_PITCHES = [(LONG_MAXB, LONG_MAXB + OVER), (65600, 65600)]
+
+
+def waves_per_packet(largest):
+    """batch.cpp Batch::waves_per_packet (frame.h tamd_frame_waves), restated:
+    `bytes <= 4096u ? 1u : bytes <= 16384u ? 2u : 4u`."""
+    return 1 if largest <= 4096 else 2 if largest <= 16384 else 4
+
+
+def add_waves(lens):
+    """An add call's shape (batch.cpp add_packets: `b->frame(nd, largest + 3)`)."""
+    return waves_per_packet(max(lens) + 3)
+
+
+def packet_waves(nbytes):
+    """The shape of an encode's output and of add_recovery (batch.cpp: the largest `o.total()`,
+    `largest_within(bytes, n, maxb)`): by the largest recovery packet as it is."""
+    return waves_per_packet(max(nbytes))
+
+
+def size_class(n):
+    """0: one wave when added (n + 3 <= 4096), 1: two waves, 2: four (n + 3 > 16384)."""
+    return add_waves([n]).bit_length() - 1
+
+
+def long_lengths(s):
+    rot = LONG_LENS[4 * s % 13:] + LONG_LENS[:4 * s % 13]
+    return (rot * 3)[:LONG_ORIG]
+
+
+def lost_long(s, i):
+    """Three sizes of each stream's first pass through LONG_LENS and three of its second: one or more of
+    every size class, 16384 and 65535 (3-byte headers) among them."""
+    return long_lengths(s)[i] in ((4093, 9000, 16384), (1, 16381, 65535), ())[i // 13]
+
+
+@pytest.fixture(scope="module")
+def long_payloads():
+    return make_payloads(N_STREAMS, long_lengths, 8)
+
+
+_long_script = []
+
+
+def long_decoder_script(long_payloads):
+    """The reference's side of test_decoder_matches_reference_on_long_packets, computed once on the
+    CPU: the reference encoders' traffic delivered round by round without the originals of
+    lost_long, each call with what RefDecoder returned (steps as in impaired_decoder_script), and
+    the originals the reference decoders recovered, (stream, number, bytes)."""
+    if not _long_script:
+        decs = [RefDecoder() for _ in range(N_STREAMS)]
+        steps, recovered = [], []
+
+        def decode_step():
+            want = [d.decode_if_ready() for d in decs]
+            recovered.extend((s, num, len(data)) for s, w in enumerate(want) for num, data in w[1])
+            steps.append(("decode", want))
+
+        for r, recs in enumerate(reference_traffic(long_payloads, LONG_ORIG)):
+            if r < LONG_ORIG // PER_CALL:
+                ent = [(s, r * PER_CALL + k) for k in range(PER_CALL) for s in range(N_STREAMS) if not lost_long(s, r * PER_CALL + k)]
+                rcs = [decs[s].add_original(i, long_payloads[s][i]) for s, i in ent]
+                assert rcs == [SUCCESS] * len(ent)
+                steps.append(("orig", [(s, i, long_payloads[s][i]) for s, i in ent], rcs))
+                decode_step()
+            steps.append(("rec", recs, [decs[s].add_recovery(d) for s, d in recs]))
+            decode_step()
+            steps.append(("ack", [d.ack() for d in decs]))
+        for d in decs:
+            d.close()
+        _long_script.append((steps, recovered))
+    return _long_script[0]
+
+
+@pytest.mark.parametrize("skew", [0, 5])
+@pytest.mark.parametrize("pitch,out_pitch", LONG_PITCHES)
+def test_encoder_matches_reference_on_long_packets(hip, long_payloads, pitch, out_pitch, skew):
+    """test_encoder_matches_reference at max_packet_bytes 65535 over LONG_LENS: every add call and
+    every encode runs four waves per packet (asserted from the call's sizes), short packets beside
+    long ones in every call."""
+    bc = new_codec(N_STREAMS, LONG_MAXB, N_STREAMS * STREAM_ARENA)
+    refs = [RefEncoder() for _ in range(N_STREAMS)]
+    ref_dec = [RefDecoder() for _ in range(N_STREAMS)]
+    src = Guarded(hip, N_STREAMS * PER_CALL * pitch, skew)
+    out = Guarded(hip, len(ENCODE_LIST) * out_pitch, skew)
+    try:
+        for r in range(LONG_ORIG // PER_CALL):
+            stream = [s for k in range(PER_CALL) for s in range(N_STREAMS)]
+            index = [r * PER_CALL + k for k in range(PER_CALL) for s in range(N_STREAMS)]
+            pk = [long_payloads[s][i] for s, i in zip(stream, index)]
+            assert add_waves([len(p) for p in pk]) == 4 and min(len(p) for p in pk) <= 4093
+            src.upload(slots(pk, pitch))
+            pn, rc = bc.encoder_add(stream, [len(p) for p in pk], src.ptr, pitch)
+            want = [refs[s].add(p) for s, p in zip(stream, pk)]
+            assert [w[0] for w in want] == [SUCCESS] * len(pk)
+            assert list(rc) == [w[0] for w in want] and list(pn) == [w[1] for w in want]
+            check_all(src, out)
+            out.fill()
+            nb, rc = bc.encode(ENCODE_LIST, out.ptr, out_pitch)
+            want = [refs[s].encode() for s in ENCODE_LIST]
+            assert [w[0] for w in want] == [SUCCESS] * len(want)
+            assert list(rc) == [w[0] for w in want], r
+            assert list(nb) == [len(w[1]) for w in want], r
+            assert packet_waves(nb) == 4 and (r == 0 or max(nb) > LONG_MAXB)
+            got = recovery_slots(out, out_pitch, nb)
+            for i, (g, w) in enumerate(zip(got, want)):
+                assert g == w[1], f"round {r} recovery packet {i} (stream {ENCODE_LIST[i]}) differs"
+            check_all(src, out)
+            for s, w in zip(ENCODE_LIST, want):
+                assert ref_dec[s].add_recovery(w[1]) == 0
+            for s in range(N_STREAMS):
+                for k in range(PER_CALL):
+                    i = r * PER_CALL + k
+                    if i not in (5, 20):
+                        assert ref_dec[s].add_original(i, long_payloads[s][i]) == 0
+            if r == 1:  # after the second add call: the receivers' acknowledgements
+                for s in range(N_STREAMS):
+                    arc, ack = ref_dec[s].ack()
+                    assert arc == 0 and ack
+                    assert bc.encoder_ack(s, ack) == refs[s].ack(ack)
+    finally:
+        bc.close()
+        for x in refs + ref_dec:
+            x.close()
+
+
+def replay_decoder_script(hip, bc, steps, n_streams, pitch, rec_pitch, skew, cap):
+    """The calls of a decoder script on the handle, each against the reference's recorded answer."""
+    most_o = max(len(st[1]) for st in steps if st[0] == "orig")
+    most_r = max(len(st[1]) for st in steps if st[0] == "rec")
+    src, rec, out = Guarded(hip, most_o * pitch, skew), Guarded(hip, most_r * rec_pitch, skew), Guarded(hip, cap * pitch, skew)
+    for n, st in enumerate(steps):
+        if st[0] == "orig":
+            ent = st[1]
+            src.upload(slots([e[2] for e in ent], pitch))
+            rc = bc.decoder_add_original([e[0] for e in ent], [e[1] for e in ent], [len(e[2]) for e in ent], src.ptr, pitch)
+            assert list(rc) == st[2], f"step {n}"
+        elif st[0] == "rec":
+            ent = st[1]
+            rec.upload(slots([e[1] for e in ent], rec_pitch))
+            rc = bc.decoder_add_recovery([e[0] for e in ent], [len(e[1]) for e in ent], rec.ptr, rec_pitch)
+            assert list(rc) == st[2], f"step {n}"
+        elif st[0] == "decode":
+            decode_and_compare(bc, [Recorded(w) for w in st[1]], out, pitch, cap, f"step {n}")
+        else:
+            assert [bc.decoder_ack(s) for s in range(n_streams)] == st[1], f"step {n}"
+        check_all(src, rec, out)
+
+
+@pytest.mark.parametrize("skew", [0, 5])
+@pytest.mark.parametrize("pitch,rec_pitch", LONG_PITCHES)
+def test_decoder_matches_reference_on_long_packets(hip, long_payloads, pitch, rec_pitch, skew):
+    """test_decoder_matches_reference at max_packet_bytes 65535 over LONG_LENS.  The reference
+    decoders alone (long_decoder_script, on the CPU) recover originals of every size class -- one
+    wave when added, two, four -- and of 16384 bytes and more, whose 3-byte length header the
+    unframing kernel reads back; the handle must return the same packets byte for byte."""
+    steps, recovered = long_decoder_script(long_payloads)
+    sizes = [n for _, _, n in recovered]
+    assert {size_class(n) for n in sizes} == {0, 1, 2} and max(sizes) >= 16384 and len(sizes) >= 12, sorted(sizes)
+    assert min(sizes) <= 4093 and any(4094 <= n <= 16381 for n in sizes) and any(n >= 16382 for n in sizes)
+    for s in range(N_STREAMS):
+        assert {size_class(n) for t, _, n in recovered if t == s} == {0, 1, 2}, s
+    assert all(rc == SUCCESS for st in steps if st[0] in ("orig", "rec") for rc in st[2])
+    for st in steps:  # every add call of either kind runs four waves per packet, short packets among them
+        if st[0] == "orig":
+            assert add_waves([len(e[2]) for e in st[1]]) == 4 and min(len(e[2]) for e in st[1]) <= 4093
+        elif st[0] == "rec":
+            assert packet_waves([len(e[1]) for e in st[1]]) == 4
+    bc = new_codec(N_STREAMS, LONG_MAXB, N_STREAMS * STREAM_ARENA)
+    try:
+        replay_decoder_script(hip, bc, steps, N_STREAMS, pitch, rec_pitch, skew, 16)
+    finally:
+        bc.close()
+
+
+class ShapeRig:
+    """One handle of max_packet_bytes 65535 beside a reference encoder and decoder per stream, for
+    single calls of a chosen launch shape."""
+    PITCH, REC_PITCH = LONG_MAXB, LONG_MAXB + OVER
+
+    def __init__(self, hip, n_streams, most_packets):
+        self.n = n_streams
+        self.bc = new_codec(n_streams, LONG_MAXB, n_streams * STREAM_ARENA)
+        self.encs = [RefEncoder() for _ in range(n_streams)]
+        self.decs = [RefDecoder() for _ in range(n_streams)]
+        self.src = Guarded(hip, most_packets * self.PITCH, 3)
+        self.rec = Guarded(hip, n_streams * self.REC_PITCH, 1)
+        self.out = Guarded(hip, n_streams * self.PITCH, 7)
+
+    def call(self, packets, withheld, ack=False):
+        """`packets` [(stream, payload)] added in one call and one recovery packet encoded for every
+        stream, both compared with the reference; then the decoder round: the packets but those at
+        the list indices `withheld` (at most one of a stream) and the recovery packets are added,
+        and decode must return the withheld ones.  With `ack` the decoders' acknowledgements go to
+        the encoders, whose windows then start behind this call's packets.  Returns the waves per
+        packet of the add call and of the recovery packets."""
+        bc, src, rec, out = self.bc, self.src, self.rec, self.out
+        bufs = (src, rec, out)
+        streams, lens = [s for s, _ in packets], [len(p) for _, p in packets]
+        src.upload(slots([p for _, p in packets], self.PITCH))
+        pn, rc = bc.encoder_add(streams, lens, src.ptr, self.PITCH)
+        want = [self.encs[s].add(p) for s, p in packets]
+        assert [w[0] for w in want] == [SUCCESS] * len(packets)
+        assert list(rc) == [w[0] for w in want] and list(pn) == [w[1] for w in want]
+        check_all(*bufs)
+        elist = list(range(self.n))
+        rec.fill()
+        nb, rc = bc.encode(elist, rec.ptr, self.REC_PITCH)
+        want_rec = [self.encs[s].encode() for s in elist]
+        assert [w[0] for w in want_rec] == [SUCCESS] * self.n
+        assert list(rc) == [w[0] for w in want_rec] and list(nb) == [len(w[1]) for w in want_rec]
+        assert recovery_slots(rec, self.REC_PITCH, nb) == [w[1] for w in want_rec]
+        check_all(*bufs)
+        # the receivers: what was not withheld, then the recovery packets out of the encode's own buffer
+        kept = [i for i in range(len(packets)) if i not in withheld]
+        if kept:
+            src.upload(slots([packets[i][1] for i in kept], self.PITCH))
+            ks, kn = [streams[i] for i in kept], [int(pn[i]) for i in kept]
+            rc = bc.decoder_add_original(ks, kn, [lens[i] for i in kept], src.ptr, self.PITCH)
+            assert list(rc) == [self.decs[s].add_original(n, packets[i][1]) for s, n, i in zip(ks, kn, kept)] == [SUCCESS] * len(kept)
+            check_all(*bufs)
+            assert decode_and_compare(bc, self.decs, out, self.PITCH, self.n, "originals") == []
+        rc = bc.decoder_add_recovery(elist, [int(x) for x in nb], rec.ptr, self.REC_PITCH)
+        assert list(rc) == [self.decs[s].add_recovery(want_rec[s][1]) for s in elist] == [SUCCESS] * self.n
+        check_all(*bufs)
+        flat = decode_and_compare(bc, self.decs, out, self.PITCH, self.n, "recovery")
+        assert flat == sorted((streams[i], int(pn[i]), packets[i][1]) for i in withheld), "the withheld packets did not come back"
+        check_all(*bufs)
+        if ack:
+            for s in elist:
+                arc, a = self.decs[s].ack()
+                assert arc == 0 and a and bc.decoder_ack(s) == (arc, a)
+                assert bc.encoder_ack(s, a) == self.encs[s].ack(a)
+        return add_waves(lens), packet_waves(nb)
+
+    def close(self):
+        self.bc.close()
+        for x in self.encs + self.decs:
+            x.close()
+
+
+def random_packets(seed, spec):
+    """spec [(stream, bytes)] -> [(stream, payload)]"""
+    rng = np.random.default_rng(seed)
+    return [(s, rng.integers(0, 256, n, dtype=np.uint8).tobytes()) for s, n in spec]
+
+
+@pytest.mark.parametrize("length,n,waves", [(9000, 1, 2), (9000, 3, 2), (9000, 5, 2), (16384, 1, 4), (16384, 3, 4), (65535, 1, 4),
+                                            (65535, 3, 4)])
+def test_launch_shapes_of_equally_long_packets(hip, length, n, waves):
+    """One stream, one call of n equally long packets: two waves per packet at 9000 bytes (n = 1, 3
+    and 5 fill half a workgroup, one and a half, two and a half), four at 16384 and 65535; from two
+    packets on they are added as a run.  The middle packet is withheld and recovered."""
+    rig = ShapeRig(hip, 1, n)
+    try:
+        assert rig.call(random_packets(length + n, [(0, length)] * n), {n // 2}) == (waves, waves)
+    finally:
+        rig.close()
+
+
+def test_short_and_long_packets_in_one_call(hip):
+    """1-byte, 17-byte and 65535-byte packets of two streams in one call: the short ones run under the
+    256 lanes of the long ones.  Stream 0 loses its 1-byte packet, stream 1 its longest."""
+    rig = ShapeRig(hip, 2, 6)
+    try:
+        spec = [(0, 1), (1, 17), (0, 65535), (1, 1), (0, 17), (1, 65535)]
+        assert rig.call(random_packets(61, spec), {0, 5}) == (4, 4)
+    finally:
+        rig.close()
+
+
+def test_launch_shape_changes_between_calls_of_one_handle(hip):
+    """Short packets only, then long ones, then short ones again on one handle: one wave per packet,
+    four, one -- in the add calls and, the windows acknowledged in between, in the recovery packets."""
+    rig = ShapeRig(hip, 2, 4)
+    try:
+        short = [(0, 100), (1, 1), (0, 17), (1, 1300)]
+        shapes = [rig.call(random_packets(62, short), {2, 3}, ack=True),
+                  rig.call(random_packets(63, [(0, 65535), (1, 40000), (0, 65535), (1, 16382)]), {0, 1}, ack=True),
+                  rig.call(random_packets(64, short), {0, 1}, ack=True)]
+        assert shapes == [(1, 1), (4, 4), (1, 1)]
+    finally:
+        rig.close()

@@ -509,3 +509,149 @@ def test_chain_compress_build_parse_decompress(hip):
     finally:
         for x in (sender, receiver, framer):
             x.close()
+
+
+# ---- 7. calls larger than one launch's scratch ----
+
+LARGE = 24000
+LZ_MAX_MESSAGE = 1536        # lz.h `#define TAMD_LZ_MAX_MESSAGE 1536u`: larger messages take scratch
+SCRATCH_BUDGET = 64 << 20    # cbatch.cpp `const size_t kScratchBudget = (size_t)64 << 20`
+
+
+def lz_scratch_bytes(n):
+    """lz.h tamd_lz_scratch_bytes: `(8u * S + 4u * ((n + 64u) / 4u + 4u) + 6u * S + 15u) & ~15u` with
+    S = tamd_lz_big_seqs(n) = `n / 4u + 1u`."""
+    S = n // 4 + 1
+    return (8 * S + 4 * ((n + 64) // 4 + 4) + 6 * S + 15) & ~15
+
+
+# cbatch.cpp tamd_cbatch_compress cuts a pass at `big && scr + big > kScratchBudget`: 620 messages of
+# 24000 bytes (108,096 bytes of scratch each) fit one launch, the 621st starts the next
+COMPRESS_FIT = SCRATCH_BUDGET // lz_scratch_bytes(LARGE)
+# cbatch.cpp tamd_cbatch_decompress: `per_launch = kScratchBudget / scratch_each` with scratch_each =
+# align16(maxb) streams in a launch, stream job k in slot `k % per_launch`: 2796, so job 2796 reuses slot 0
+DECOMPRESS_FIT = SCRATCH_BUDGET // ((LARGE + 15) & ~15)
+EXTRA = 3  # streams beyond the large call's, for the small calls around it
+
+
+def large_templates():
+    """Nine streams of two messages of 24000 bytes in the style of streams_sealed: stretches of
+    words, of random bytes and repeats of earlier stretches (the second message's reach into the
+    first), the last seven bytes random.  The ninth stream's first message is random throughout:
+    it is sent as is."""
+    if "templates" not in _cache:
+        words = [b"siamese ", b"tonk ", b"packet ", b"recovery ", b"window ", b"lane ", b"sum ", b"ack ", b"0123 "]
+        out = []
+        for t in range(9):
+            rng = np.random.default_rng(900 + t)
+            stream, msgs = bytearray(), []
+            for k in range(2):
+                m = bytearray()
+                while len(m) < LARGE - 7:
+                    kind, ln = int(rng.integers(0, 3)), int(rng.integers(200, 2500))
+                    if t == 8 and k == 0:
+                        kind, ln = 1, LARGE
+                    if kind == 0:
+                        piece = b"".join(words[int(i)] for i in rng.integers(0, len(words), ln // 4))[:ln]
+                    elif kind == 1 or len(stream) + len(m) < 4000:
+                        piece = rng.integers(0, 256, min(ln, 700) if t < 8 else ln, dtype=np.uint8).tobytes()
+                    else:
+                        whole = bytes(stream) + bytes(m)
+                        start = int(rng.integers(max(0, len(whole) - 30000), len(whole) - 100))
+                        piece = whole[start:start + ln]
+                    m += piece
+                m = bytes(m[:LARGE - 7]) + rng.integers(0, 256, 7, dtype=np.uint8).tobytes()
+                stream += m
+                msgs.append(m)
+            out.append(msgs)
+        _cache["templates"] = out
+    return _cache["templates"]
+
+
+def test_compress_call_larger_than_one_launchs_scratch(hip, L):
+    """One call with a 24000-byte message for each of COMPRESS_FIT + 2 = 622 fresh streams of one
+    pass takes two compression launches (asserted); a call of three streams before it and one of
+    four after it on the same handle make the staging and the scratch grow and be used again.
+    Every block is the first (after: the second) block of a MessageCompressor drop-in for the
+    stream's template, and the reference decompressor restores it."""
+    import tonk_amd
+    from tonk_amd import cbatch
+    from tonk_amd.compress import MessageCompressor
+    assert lz_scratch_bytes(LARGE) == 108096 and COMPRESS_FIT == 620 and LARGE > LZ_MAX_MESSAGE
+    n_big = COMPRESS_FIT + 2
+    templates = large_templates()[:8]
+    comps = [MessageCompressor(LARGE) for _ in templates]
+    want = [[c.compress(m) for m in msgs] for c, msgs in zip(comps, templates)]
+    for c in comps:
+        c.close()
+    assert all(0 < len(b) < LARGE for bs in want for b in bs), [[len(b) for b in bs] for bs in want]
+    for msgs, bs in zip(templates, want):
+        restores(L, LARGE, msgs, bs)
+    streams = [templates[s % 8] for s in range(n_big + EXTRA)]
+    h = tonk_amd.BatchCompressor(n_big + EXTRA, LARGE, sides=cbatch.COMPRESS, abut=False)
+    h.set_timing(True)
+    try:
+        def call(items, first):
+            h.kernel_ms()
+            got = compress_call(hip, h, streams, items, LARGE + 3, first=first)
+            for (s, k), b in zip(items, got):
+                assert len(b) > 0 and b == want[s % 8][k], (s, k, len(b), len(want[s % 8][k]))
+            return h.kernel_ms()["compress_launches"]
+
+        assert call([(n_big + e, 0) for e in range(EXTRA)], 1) == 1
+        assert call([(s, 0) for s in range(n_big)], 2) == -(-n_big // COMPRESS_FIT) == 2
+        assert call([(n_big, 1), (n_big + 1, 1), (0, 1), (n_big - 1, 1)], 3) == 1
+    finally:
+        h.close()
+
+
+def test_decompress_call_larger_than_one_launchs_scratch(hip, L):
+    """One call with one item for each of DECOMPRESS_FIT + 1 = 2797 streams takes two launches
+    (asserted) whose jobs reuse the scratch slots: streams 0 and 2796 share slot 0.  The items are
+    the reference compressor's blocks of the templates (all restore to 24000 bytes: literals in
+    scratch) and, every 97th, a message sent as is.  A second call gives a subset of the streams
+    their second message: each kept its own history.  Small calls on three more streams before and
+    after."""
+    import tonk_amd
+    from tonk_amd import cbatch
+    assert DECOMPRESS_FIT == 2796
+    n_big = DECOMPRESS_FIT + 1
+    templates = large_templates()
+    blocks = []
+    for msgs in templates:
+        c = RefCompressor(L, LARGE)
+        blocks.append([c.compress(m) for m in msgs])
+    assert all(b for bs in blocks[:8] for b in bs) and not blocks[8][0] and blocks[8][1]
+    template_of = lambda s: 8 if s % 97 == 5 else s % 8
+    as_is = [s for s in range(n_big) if template_of(s) == 8]
+    assert 3 <= len(as_is) <= n_big // 20 and 0 not in as_is and DECOMPRESS_FIT not in as_is
+    assert sum(1 for s in range(n_big) if len(templates[template_of(s)][0]) > LZ_MAX_MESSAGE and blocks[template_of(s)][0]) >= n_big // 2
+
+    def item(s, k):
+        b = blocks[template_of(s)][k]
+        return (s, 1 if b else 0, b or templates[template_of(s)][k])
+
+    h = tonk_amd.BatchCompressor(n_big + EXTRA, LARGE, sides=cbatch.DECOMPRESS)
+    h.set_timing(True)
+    try:
+        def call(entries, first):
+            h.kernel_ms()
+            res = decompress_call(hip, h, [item(s, k) for s, k in entries], LARGE + 5, first=first)
+            for (s, k), (status, out) in zip(entries, res):
+                assert status == 0, (s, k, status)
+                if blocks[template_of(s)][k]:
+                    assert out == templates[template_of(s)][k], (s, k)
+                else:
+                    assert out is None
+            return h.kernel_ms()["decompress_launches"], res
+
+        assert call([(n_big + e, 0) for e in range(EXTRA)], 1)[0] == 1
+        launches, res = call([(s, 0) for s in range(n_big)], 2)
+        assert launches == -(-n_big // DECOMPRESS_FIT) == 2
+        # slot 0's two users: the streams are listed in order, so job k is stream k
+        assert res[0][1] == templates[template_of(0)][0] and res[DECOMPRESS_FIT][1] == templates[template_of(DECOMPRESS_FIT)][0]
+        again = sorted({0, DECOMPRESS_FIT, DECOMPRESS_FIT - 1, 1} | set(as_is[:2]) | set(range(7, n_big, 131)))
+        assert call([(s, 1) for s in again], 3)[0] == 1
+        assert call([(n_big + e, 1) for e in range(EXTRA)] + [(2, 1)], 4)[0] == 1
+    finally:
+        h.close()

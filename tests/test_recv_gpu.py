@@ -391,3 +391,139 @@ def test_soak_shuffled_with_loss_repeats_and_bad_tags(hip, factory):
     assert {0, 2, 3} <= seen
     assert rx.kernel_ms()["repaired_tags"] >= 1
     rx.close()
+
+
+# ---- 7. datagrams above 1400 bytes ----
+
+LONG_MAXB = 65535
+TAG_TILE = 128  # seal.h TAMD_SEAL_TILE: tamd_rx_tag hashes a group's datagrams in tiles of 128 bytes
+
+
+class LongFactory:
+    """Datagrams of up to 65535 bytes: a random body (a message frame holds at most 2047 bytes, and
+    the receive front does not look inside) behind the footer dgram_ref lays, ciphered and tagged
+    on the device by DatagramSealer.seal, which its own test proves at 65535."""
+
+    def __init__(self, hip):
+        import tonk_amd
+        self.hip = hip
+        self.sealer = tonk_amd.DatagramSealer(N_STREAMS, LONG_MAXB)
+        for s in range(N_STREAMS):
+            self.sealer.set_key(s, key_of(s))
+        self.rng = np.random.default_rng(20261)
+
+    def make(self, specs):
+        """specs: dicts(stream, nonce, nb, sb, bytes).  Returns the sealed datagrams as uint8 arrays."""
+        import dgram_ref as D
+        n, pitch = len(specs), max(s["bytes"] for s in specs) + 3
+        plain = np.full(n * pitch, FILL, dtype=np.uint8)
+        msgs = []
+        for i, s in enumerate(specs):
+            M = s["bytes"] - 6 - s["nb"] - s["sb"]
+            assert M >= 0, s
+            foot = D.footer(7 + i, s["sb"], s["nonce"], s["nb"], None, (i * 2654435761 + 99) & 0xFFFFFF, D.ONLYFEC if i % 3 == 0 else 0)
+            plain[i * pitch:i * pitch + M] = self.rng.integers(0, 256, M, dtype=np.uint8)
+            plain[i * pitch + M:i * pitch + s["bytes"]] = np.frombuffer(foot, dtype=np.uint8)
+            msgs.append(M)
+        buf = Guarded(self.hip, n * pitch, 5)
+        buf.upload(plain)
+        rc = self.sealer.seal([s["stream"] for s in specs], [s["nonce"] for s in specs], [s["bytes"] for s in specs], msgs, buf.ptr, pitch)
+        assert (rc == 0).all()
+        sealed = buf.download()
+        buf.check()
+        return [sealed[i * pitch:i * pitch + s["bytes"]].copy() for i, s in enumerate(specs)]
+
+    def close(self):
+        self.sealer.close()
+
+
+@pytest.fixture(scope="module")
+def long_factory(hip):
+    f = LongFactory(hip)
+    yield f
+    f.close()
+
+
+def short_specs(n, streams, first_nonce=1):
+    """n datagrams of 6 to 40 bytes over `streams` in turn, nonces counting up per stream."""
+    specs, nonce = [], {s: first_nonce - 1 for s in streams}
+    for k in range(n):
+        s, nbytes = streams[k % len(streams)], 6 + k % 35
+        nb = min(k % 4, nbytes - 6)
+        nonce[s] += 1
+        specs.append(dict(stream=s, nonce=nonce[s], nb=nb, sb=min((k // 4) % 4, nbytes - 6 - nb), bytes=nbytes))
+    return specs
+
+
+def test_long_datagrams_at_the_tile_edges_with_every_nonce_width(hip, long_factory):
+    """The tagged part (bytes - 6) one below, at and one above 11, 12, 32 and 511 tiles of 128 bytes,
+    around 2048, and the two longest datagrams, each with 0, 1, 2 and 3 nonce bytes; in three
+    calls, each one group of 64 whose longest datagram sets the tile loop's length for all."""
+    tagged = [TAG_TILE * k + e for k in (11, 12, 32, 511) for e in (-1, 0, 1)] + [2047, 2048, 2049, 65534 - 6, 65535 - 6]
+    assert max(tagged) == LONG_MAXB - 6 and (max(tagged) + TAG_TILE - 1) // TAG_TILE == 512
+    rx, model = receiver(maxb=LONG_MAXB), fresh_model()
+    raw = [dict(stream=(k + nb) % 3, nb=nb, sb=(k + 2 * nb) % 4, bytes=t + 6) for k, t in enumerate(tagged) for nb in range(4)]
+    specs, nonce = [], [0, 0, 0]  # keys {0, non-zero, non-zero}
+    for spec in raw[0::3] + raw[1::3] + raw[2::3]:  # (every third of the list holds short and long ones alike)
+        nonce[spec["stream"]] += 1
+        specs.append(dict(spec, nonce=nonce[spec["stream"]]))
+    assert {(s["bytes"], s["nb"]) for s in specs} == {(t + 6, nb) for t in tagged for nb in range(4)}
+    wires = long_factory.make(specs)
+    items = [(s["stream"], w) for s, w in zip(specs, wires)]
+    third = (len(items) + 2) // 3
+    assert third <= 64
+    for part, skew in ((items[:third], 1), (items[third:2 * third], 8), (items[2 * third:], 15)):
+        assert max(w.size for _, w in part) >= 65000 and min(w.size for _, w in part) <= 4200
+        rc, result = check_call(hip, rx, model, part, LONG_MAXB + 4, skew, maxb=LONG_MAXB)
+        assert (rc == 0).all()
+    assert rx.kernel_ms()["repaired_tags"] == 0
+    rx.close()
+
+
+def test_a_long_datagram_shares_its_group_with_short_ones(hip, long_factory):
+    """One datagram of 65535 bytes and 63 of 6 to 40 bytes of other streams in the first group of 64
+    (512 tiles for all of them), a second group of short ones only."""
+    rx, model = receiver(maxb=LONG_MAXB), fresh_model()
+    long_one = long_factory.make([dict(stream=0, nonce=1, nb=2, sb=1, bytes=LONG_MAXB)])[0]
+    specs = short_specs(127, list(range(1, N_STREAMS)))
+    shorts = [(s["stream"], w) for s, w in zip(specs, long_factory.make(specs))]
+    at = 37
+    items = shorts[:at] + [(0, long_one)] + shorts[at:]
+    assert len(items) == 128 and at // 64 == 0 and items[at][1].size == LONG_MAXB
+    assert all(6 <= w.size <= 40 for i, (_, w) in enumerate(items) if i != at)
+    rc, _ = check_call(hip, rx, model, items, LONG_MAXB, 9, maxb=LONG_MAXB)
+    assert (rc == 0).all()
+    rx.close()
+
+
+def test_repair_duplicate_and_oversize_on_long_datagrams(hip, long_factory):
+    """Stream 1 sends 65535, 40000 and 65535 bytes, each in another group of 64; the first one's tag is
+    corrupted, so the later two are resolved under another nonce than the guess (the one-lane
+    repair hash and the decipher at length).  The second comes again at the end of the call and
+    stays ciphertext.  A receiver whose maximum is one byte less refuses it untouched."""
+    rx, model = receiver(maxb=LONG_MAXB), fresh_model([100] * N_STREAMS)
+    for s in range(N_STREAMS):
+        rx.reset(s, 100)
+    trio = [dict(stream=1, nonce=300, nb=2, sb=0, bytes=LONG_MAXB), dict(stream=1, nonce=110, nb=1, sb=0, bytes=40000),
+            dict(stream=1, nonce=111, nb=1, sb=1, bytes=LONG_MAXB)]
+    w = long_factory.make(trio)
+    specs = short_specs(128, list(range(2, 10)), 101)
+    fill = [(s["stream"], x) for s, x in zip(specs, long_factory.make(specs))]
+    items = [(1, corrupt(w[0]))] + fill[:64] + [(1, w[1])] + fill[64:] + [(1, w[2]), (1, w[1])]
+    where = [i for i, (s, _) in enumerate(items) if s == 1]
+    assert [i // 64 for i in where] == [0, 1, 2, 2]
+    # the guess takes the first for good: the second's nonce byte would expand under 300, not under 100
+    assert R.expand(300, 110 & 0xFF, 1) != 110 == R.expand(100, 110 & 0xFF, 1)
+    rx.kernel_ms()
+    rc, result = check_call(hip, rx, model, items, LONG_MAXB + 1, 7, maxb=LONG_MAXB)
+    assert [int(rc[i]) for i in where] == [2, 0, 0, 3]
+    assert [int(result["nonce"][i]) for i in where[1:]] == [110, 111, 110]
+    assert rx.kernel_ms()["repaired_tags"] >= 1
+    assert KEYS[1] and model[1].reg.largest == 111
+    rx.close()
+    small, small_model = receiver(maxb=40000 - 1), fresh_model([100] * N_STREAMS)
+    for s in range(N_STREAMS):
+        small.reset(s, 100)
+    rc, _ = check_call(hip, small, small_model, [(1, w[1]), fill[0]], 40000 + 5, 2, maxb=40000 - 1)
+    assert list(rc) == [1, 0]
+    small.close()

@@ -84,8 +84,9 @@ struct Batch {
         return ok();
     }
 
-    static uint32_t waves_per_packet(uint32_t bytes) { return bytes <= 4096u ? 1u : bytes <= 16384u ? 2u : 4u; }
-    static uint32_t grid(size_t n, uint32_t wpp) { return (uint32_t)((n * wpp + 3) / 4); }
+    // (frame.h: the launch shape, shared with the host walk of the tests)
+    static uint32_t waves_per_packet(uint32_t bytes) { return tamd_frame_waves(bytes); }
+    static uint32_t grid(size_t n, uint32_t wpp) { return tamd_frame_grid(n, wpp); }
 
     // tamd_frame_rows over `d` (already in desc.host); enqueued only.
     void frame(size_t n, uint32_t largest) {

@@ -7,7 +7,8 @@
 //
 // The functions are written for `nl` cooperating lanes (lane = 0..nl-1) that all call them with
 // the same arguments and share nothing: the 16-byte chunks of a row or a slot are strided over the
-// lanes.  The kernels run them with one or a few waves per packet; on the host nl = 1.  No libc.
+// lanes.  The kernels run them with one or a few waves per packet; on the host nl = 1 (the tests'
+// walk also calls the 64, 128 and 256 lanes of a packet one after the other).  No libc.
 //
 // Memory is read in aligned 16-byte granules: a granule is read when at least one of its bytes
 // belongs to the packet, so a read never leaves the aligned 16 bytes around the packet's first
@@ -29,6 +30,19 @@
 #define TAMD_FRAME_E_EMPTY 2u   // the header announces 0 bytes
 #define TAMD_FRAME_E_BOUND 3u   // header + length reach beyond the row's upper bound
 #define TAMD_FRAME_E_PITCH 4u   // the length is more than a slot of the caller holds
+
+// The framing kernels' launch shape: blocks of TAMD_FRAME_BLOCK threads, one, two or four waves of
+// 64 lanes per packet (`wpp`) by the call's largest packet, whole packets per block.
+#define TAMD_FRAME_BLOCK 256u
+TAMD_FRAME_FN uint32_t tamd_frame_waves(uint32_t bytes) { return bytes <= 4096u ? 1u : bytes <= 16384u ? 2u : 4u; }
+TAMD_FRAME_FN uint32_t tamd_frame_grid(uint64_t n, uint32_t wpp) { return (uint32_t)((n * wpp + 3u) / 4u); }
+// (packet index, lane within the packet's 64 * wpp lanes) of thread `thread` of block `block`;
+// wpp divides the waves of a block.
+TAMD_FRAME_FN uint32_t tamd_frame_packet(uint32_t block, uint32_t thread, uint32_t wpp, uint32_t* lane) {
+    const uint32_t wave = block * (TAMD_FRAME_BLOCK / 64u) + thread / 64u;
+    *lane = (wave % wpp) * 64u + (thread & 63u);
+    return wave / wpp;
+}
 
 typedef struct tamd_v16 { uint32_t w[4]; } __attribute__((aligned(16))) tamd_v16;
 

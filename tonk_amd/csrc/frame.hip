@@ -5,13 +5,9 @@
 #include "kernel_abi.h"
 #include "frame.h"
 
-#define TAMD_FRAME_BLOCK 256u
-
-// (packet index, lane within the packet's lanes) of this thread; wpp divides the waves of a block
+// (packet index, lane within the packet's lanes) of this thread: frame.h's arithmetic
 __device__ __forceinline__ uint32_t frame_packet(uint32_t wpp, uint32_t* lane) {
-    const uint32_t wave = blockIdx.x * (TAMD_FRAME_BLOCK / 64u) + threadIdx.x / 64u;
-    *lane = (wave % wpp) * 64u + (threadIdx.x & 63u);
-    return wave / wpp;
+    return tamd_frame_packet(blockIdx.x, threadIdx.x, wpp, lane);
 }
 
 // Packet -> arena row: varint(len) || payload || zeros to the row's capacity (raw: no header).
